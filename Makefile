@@ -59,8 +59,8 @@ health: ## gRPC health probe of $(SERVER_ADDR) (grpc_health_probe contract)
 bench: build ## headline benchmark on 1 GPU (output tokens/s via gRPC, Llama-3-8B)
 	$(PY) bench.py --gpus 1
 
-bench-gpu8: build ## 1/2/4/8-GPU weak-scaling curve
-	for n in 1 2 4 8; do $(PY) bench.py --gpus $$n --steps 3 --warmup 1; done
+bench-gpu8: build ## 1/2/4/8-GPU weak-scaling curve (--full: plus the tp{N} 70B and ep{N} Mixtral configs)
+	for n in 1 2 4 8; do $(PY) bench.py --gpus $$n --steps 3 --warmup 1 --full; done
 
 prof: build ## rocprofv3 kernel trace + stats of a short bench run into gpurun_out/prof
 	cd /tmp && TMPDIR=/tmp rocprofv3 --kernel-trace --stats --output-format csv -d $(CURDIR)/gpurun_out/prof -o run \

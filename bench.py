@@ -17,15 +17,21 @@ random-init weights, synthetic token ids — no network for checkpoints/datasets
 W warmup waves run untimed; then K waves are timed between a barrier + device sync on both
 sides; elapsed = max over ranks; value = total output tokens of all replicas / elapsed.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K waves and prints the one JSON line (``ms_per_step``:
+milliseconds per timed wave).  ``--dump-outputs DIR`` also writes the token ids the last timed
+wave returned to its callers as ``DIR/token_ids.npy`` (float32, one row per request in submit
+order): prompts and weights are seeded, so two builds run with the same arguments can be
+compared output for output.  Everything else the benchmark measures is behind ``--full``.
 
 With N > 1 (plain, or rank 0 of the driver's torchrun -- the other outer ranks exit without
 touching a GPU) the measurement runs in a fresh N-rank torchrun child whose JSON line is relayed;
-with ``--tp 1`` a second child then serves ``--tp-extra-model`` (default Llama-3-70B) at TP = N
-over the same gRPC load and its result is added under ``tp{N}_70b`` -- the 70B TP=8 half of the
-BASELINE metric on an 8-GPU node -- and a third child serves ``--ep-extra-model`` (default
-Mixtral-8x7B) with DP attention + expert parallelism over all N GPUs (IPC expert all-to-all),
+with ``--full`` and ``--tp 1`` a second child then serves ``--tp-extra-model`` (default
+Llama-3-70B) at TP = N over the same gRPC load and its result is added under ``tp{N}_70b`` -- the
+70B TP=8 half of the BASELINE metric on an 8-GPU node -- and a third child serves
+``--ep-extra-model`` (default Mixtral-8x7B) with DP attention + expert parallelism over all N GPUs (IPC expert all-to-all),
 reported under ``ep{N}_mixtral`` (BASELINE config 5).  Each child has its own timeout inside ONE
 deadline: an extra child's failure is reported in its key and never loses the replica number.
 """
@@ -99,6 +105,14 @@ def parse_args(argv=None):
                     help="N > 1: seconds the whole run may take, below the driver's 600 s command limit. The main "
                          "child gets at most this minus a print margin, the TP child only what is left, so the "
                          "JSON line is always printed in time")
+    ap.add_argument("--full", action="store_true",
+                    help="N > 1 with --tp 1: also measure the other BASELINE configs (the tp{N} / ep{N} children "
+                         "below); a plain run measures the headline number alone")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed waves, write what the last one returned to its callers -- the generated "
+                         "token ids, one row per request in submit order -- as DIR/token_ids.npy (float32, -1 "
+                         "padded; token_ids_rank{r}.npy per serving rank when N > 1; --mode openai: the completion "
+                         "text's code points as DIR/text_codepoints.npy).  Needs --client inproc")
     ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)  # internal: the measuring torchrun job
     return ap.parse_args(argv)
 
@@ -189,7 +203,8 @@ def _extra_key(prefix: str, n: int, model: str) -> str:
 def orchestrate(args, argv) -> int:
     """``--gpus N`` (N > 1), plain or under the driver's torchrun (rank 0 only: the other outer
     ranks exit without touching a GPU).  The measurement runs as a fresh N-rank torchrun child
-    whose JSON line is relayed; with ``--tp 1`` two more children then measure the other BASELINE
+    whose JSON line is relayed; with ``--full`` and ``--tp 1`` two more children then measure the
+    other BASELINE
     configs on the same N GPUs: ``--tp-extra-model`` at TP = N (70B TP=8 on an 8-GPU node) under
     ``tp{N}_<model>`` and ``--ep-extra-model`` with DP attention + EP = N (Mixtral expert
     all-to-all) under ``ep{N}_<model>``.  Each child has its own timeout, so an extra child's
@@ -206,7 +221,7 @@ def orchestrate(args, argv) -> int:
         print(f"bench: measurement child failed (rc {rc})", file=sys.stderr)
         return rc or 1
     strip = {"--model", "--tp", "--ep", "--frontend", "--tp-extra-model", "--ep-extra-model", "--mode",
-             "--tp-extra-mode"}
+             "--tp-extra-mode", "--dump-outputs"}  # (the dump is the main measurement's alone)
 
     def extra_child(key: str, cargs, timeout: float) -> None:
         budget = min(timeout, left())
@@ -231,7 +246,7 @@ def orchestrate(args, argv) -> int:
             main_line[key] = {"error": f"child rc {trc}" + (f" (timeout after {budget:.0f} s)" if trc == 124 else ""),
                               "wall_s": round(wall, 1)}
 
-    if args.tp == 1 and args.ep == 1:
+    if args.full and args.tp == 1 and args.ep == 1:
         extra = args.tp_extra_model
         if extra == "auto":
             extra = "llama3-70b" if args.model == "llama3-8b" else "none"
@@ -254,7 +269,36 @@ async def _abarrier(group) -> None:
     await asyncio.get_running_loop().run_in_executor(None, lambda: dist.barrier(group=group))
 
 
-async def run_waves(args, engine, st, leaders_group, llm=None, n_replicas=1):
+def _outputs_array(args, raw):
+    """The last timed wave's responses as one float32 array, a row per request in submit order
+    (-1 padded): the generated token ids, or with ``--mode openai`` (a route that returns text
+    only) the completion text's code points."""
+    import numpy as np
+    if args.mode == "openai":
+        rows = [[ord(c) for c in (body["choices"][0]["message"].get("content") or "")] for body in raw]
+    else:
+        rows = [[int(v.number_value) for v in resp.struct_output.fields["token_ids"].list_value.values]
+                for resp in raw]
+    arr = np.full((len(rows), max([len(r) for r in rows] + [1])), -1.0, dtype=np.float32)
+    for i, r in enumerate(rows):
+        arr[i, :len(r)] = r
+    return arr
+
+
+def _write_outputs(args, st, n_writers: int, arr) -> None:
+    """``--dump-outputs``: at most 64 MB over all writing ranks (a larger output: a fixed, seeded
+    sample of its rows, in order)."""
+    import numpy as np
+    cap = (64 << 20) // max(n_writers, 1)
+    if arr.nbytes > cap:
+        keep = max(1, cap // max(arr.shape[1] * arr.itemsize, 1))
+        arr = arr[np.sort(np.random.default_rng(0).choice(arr.shape[0], size=keep, replace=False))]
+    os.makedirs(args.dump_outputs, exist_ok=True)
+    stem = "text_codepoints" if args.mode == "openai" else "token_ids"
+    np.save(os.path.join(args.dump_outputs, stem + (f"_rank{st.rank}" if n_writers > 1 else "") + ".npy"), arr)
+
+
+async def run_waves(args, engine, st, leaders_group, llm=None, n_replicas=1, sink=None):
     import grpc
     import torch
     import torch.distributed as dist
@@ -323,7 +367,7 @@ async def run_waves(args, engine, st, leaders_group, llm=None, n_replicas=1):
     timing = os.environ.get("POLYKEY_BENCH_TIMING") == "1"
     marks = []
 
-    def build():
+    def build(ids=False):
         if args.mode == "openai":
             n = max(1, args.prompt_len - overhead)
             text = "".join(rng.choice("abcdefghijklmnopqrstuvwxyz ") for _ in range(n))
@@ -333,6 +377,8 @@ async def run_waves(args, engine, st, leaders_group, llm=None, n_replicas=1):
         req.parameters.update({"prompt_token_ids": [rng.randrange(0, V) for _ in range(args.prompt_len)],
                                "max_tokens": args.max_tokens, "ignore_eos": True, "temperature": 0.0,
                                "return": "struct"})
+        if ids:  # --dump-outputs: the last timed wave's responses carry the generated ids themselves
+            req.parameters.update({"return_token_ids": True})
         return req
 
     async def one(req):
@@ -342,7 +388,7 @@ async def run_waves(args, engine, st, leaders_group, llm=None, n_replicas=1):
                 body = await hr.json()
             if hr.status != 200:
                 raise RuntimeError(f"openai route: HTTP {hr.status}: {body}")
-            return int(body["usage"]["completion_tokens"]), time.perf_counter() - t0
+            return int(body["usage"]["completion_tokens"]), time.perf_counter() - t0, body
         if args.mode == "unary":
             resp = await unary(req, timeout=600)
         else:
@@ -355,7 +401,7 @@ async def run_waves(args, engine, st, leaders_group, llm=None, n_replicas=1):
         if timing:
             m = proto.struct_to_dict(resp.struct_output)["metrics"]
             marks.append((t0, t1, m))
-        return int(usage["completion_tokens"].number_value), dt
+        return int(usage["completion_tokens"].number_value), dt, resp
 
     async def wave(reqs):
         marks.clear()
@@ -378,23 +424,23 @@ async def run_waves(args, engine, st, leaders_group, llm=None, n_replicas=1):
                   f"(request leg {1e3 * rin[len(rin) // 2]:.2f}/{1e3 * rin[-1]:.2f}, response leg "
                   f"{1e3 * rout[len(rout) // 2]:.2f}/{1e3 * rout[-1]:.2f}) | "
                   f"last response +{1e3 * (max(m[1] for m in marks) - tw):.1f} ms", file=sys.stderr, flush=True)
-        return sum(r[0] for r in res), [r[1] for r in res]
+        return sum(r[0] for r in res), [r[1] for r in res], [r[2] for r in res]
 
     for _ in range(args.warmup):
         await wave([build() for _ in range(conc)])
     # the load generator prepares its synthetic requests up front, as a separate client
     # process would: building 64 x 256 random ids inside a wave would only steal the event
     # loop (and the GIL) from the server under test
-    waves = [[build() for _ in range(conc)] for _ in range(args.steps)]
+    waves = [[build(ids=sink is not None and k == args.steps - 1) for _ in range(conc)] for k in range(args.steps)]
     dev = engine.device
     if sync_ranks:
         await _abarrier(leaders_group)
     if dev.type == "cuda":
         torch.cuda.synchronize(dev)
     t0 = time.perf_counter()
-    tokens, lats = 0, []
+    tokens, lats, raw = 0, [], []
     for reqs in waves:
-        n, l = await wave(reqs)
+        n, l, raw = await wave(reqs)
         tokens += n
         lats += l
     if dev.type == "cuda":
@@ -402,6 +448,8 @@ async def run_waves(args, engine, st, leaders_group, llm=None, n_replicas=1):
     if sync_ranks:
         await _abarrier(leaders_group)
     elapsed = time.perf_counter() - t0
+    if sink is not None and raw:
+        sink.append(_outputs_array(args, raw))
     await channel.close()
     if session is not None:
         await session.close()
@@ -466,6 +514,8 @@ async def _drive_external(args, engine, st, leaders_group, port, srv, llm, conc,
 def main(argv=None) -> int:
     argv = list(sys.argv[1:] if argv is None else argv)
     args = parse_args(argv)
+    if args.dump_outputs and args.client == "process":
+        raise SystemExit("--dump-outputs needs --client inproc: a load-generator process keeps its responses")
     if args.gpus > 1 and not args.child:
         if int(os.environ.get("RANK", "0")) != 0:
             return 0  # under the driver's torchrun: rank 0 runs the measurement children
@@ -506,6 +556,7 @@ def main(argv=None) -> int:
         while True:  # a hung TP child (tests: the orchestrator's deadline must still print the line)
             time.sleep(60)
     leaders = list(range(0, st.world_size, st.tp_size))
+    sink = [] if args.dump_outputs else None  # receives the last timed wave's outputs on a serving rank
     leaders_group = dist.new_group(leaders) if dist.is_initialized() else None
     dp_front = st.world_size > 1 and st.tp_size == 1 and not engine.lockstep
     if args.frontend == "single" and dp_front:
@@ -517,12 +568,13 @@ def main(argv=None) -> int:
             local.shutdown()
             tokens, elapsed, lats = 0, 0.0, []
         else:
-            tokens, elapsed, lats = asyncio.run(run_waves(args, engine, st, None, llm=pool, n_replicas=st.world_size))
+            tokens, elapsed, lats = asyncio.run(run_waves(args, engine, st, None, llm=pool, n_replicas=st.world_size,
+                                                          sink=sink))
     elif st.tp_rank != 0:
         engine.runner.worker_loop()
         tokens, elapsed, lats = 0, 0.0, []
     else:
-        tokens, elapsed, lats = asyncio.run(run_waves(args, engine, st, leaders_group))
+        tokens, elapsed, lats = asyncio.run(run_waves(args, engine, st, leaders_group, sink=sink))
         engine.runner.stop_workers()
 
     if dist.is_initialized():
@@ -535,6 +587,8 @@ def main(argv=None) -> int:
         cached = sum(x[3] for x in allr)
     else:
         cached = engine.scheduler.num_cached_tokens
+    if sink:
+        _write_outputs(args, st, 1 if args.frontend == "single" and dp_front else len(leaders), sink[0])
     if st.rank == 0:
         p50 = statistics.median(lats) if lats else None
         value = tokens / elapsed if elapsed > 0 else 0.0

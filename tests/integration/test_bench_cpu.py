@@ -57,6 +57,32 @@ def test_bench_json_line(tmp_path, gpus, client, frontend):
     assert out["value"] == pytest.approx(4 * 4 * gpus / (out["ms_per_step"] / 1000.0), rel=0.02)
 
 
+def test_bench_dump_outputs_is_reproducible(tmp_path):
+    """--dump-outputs writes the token ids the last timed wave returned (one float32 row per request,
+    every request its --max-tokens ids inside the vocabulary); seeded prompts and weights: a second
+    run with the same arguments writes the same array."""
+    import numpy as np
+    env = dict(os.environ, CUDA_VISIBLE_DEVICES="", HIP_VISIBLE_DEVICES="")
+    dumps = []
+    for d in ("a", "b"):
+        r = _run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--dump-outputs", str(tmp_path / d)]
+                 + ARGS[:3] + ["2"] + ARGS[4:], tmp_path, env)
+        assert r.returncode == 0, r.stderr[-2000:]
+        out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
+        # --steps sets the number of timed waves: 2 waves of 4 requests x 4 tokens in 2 x ms_per_step
+        assert out["steps"] == 2
+        assert out["value"] == pytest.approx(2 * 4 * 4 / (2 * out["ms_per_step"] / 1000.0), rel=0.02)
+        assert os.listdir(tmp_path / d) == ["token_ids.npy"]
+        dumps.append(np.load(tmp_path / d / "token_ids.npy"))
+    a, b = dumps
+    assert a.dtype == np.float32 and a.shape == (4, 4)
+    assert (a >= 0).all() and (a == np.floor(a)).all() and a.max() < 1 << 20
+    assert np.array_equal(a, b)
+    r = _run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--client", "process", "--dump-outputs",
+              str(tmp_path / "c")] + ARGS, tmp_path, env)
+    assert r.returncode != 0 and "--client inproc" in r.stderr
+
+
 def test_bench_openai_chat_route():
     """VERDICT r5 item 8 / BASELINE config 4's route: --mode openai drives POST /v1/chat/completions
     (api/openai.py on the server's process) with templated prompts of exactly --prompt-len tokens;
@@ -85,7 +111,7 @@ def test_bench_dp_attention_expert_all_to_all():
 
 
 def test_bench_world8_reports_tp_child():
-    """The 8-GPU driver launch (torchrun, 8 ranks running bench.py --gpus 8) on the CPU: rank 0
+    """The 8-GPU driver launch (torchrun, 8 ranks running bench.py --gpus 8 --full) on the CPU: rank 0
     relays the replica measurement of a fresh 8-rank child and adds the TP=8 child's result under
     tp8_<model> (a 70B-shaped tiny model: 8 kv heads, GQA 8, ragged vocab); a TP child that fails
     leaves the replica number intact."""
@@ -93,7 +119,8 @@ def test_bench_world8_reports_tp_child():
     base = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=8",
             "--master-addr", "127.0.0.1", "--master-port", "0", os.path.join(REPO, "bench.py"), "--gpus", "8",
             "--model", "tiny-llama-g8", "--steps", "1", "--warmup", "1", "--concurrency", "2", "--prompt-len", "128",
-            "--max-tokens", "3", "--no-graphs"]  # (128: the TP child's chat template alone is 100 byte tokens)
+            "--max-tokens", "3", "--no-graphs", "--full"]  # (128: the TP child's chat template alone is 100 byte
+    # tokens; --full: the tp8 / ep8 children run only in a full benchmark)
     r = _run(base + ["--tp-extra-model", "tiny-llama-g8", "--ep-extra-model", "tiny-mixtral-e8"], REPO, env,
              timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -131,7 +158,8 @@ def test_bench_world8_hung_tp_child_meets_the_deadline():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=8", "--master-addr",
            "127.0.0.1", "--master-port", "0", os.path.join(REPO, "bench.py"), "--gpus", "8", "--model",
            "tiny-llama-g8", "--steps", "1", "--warmup", "1", "--concurrency", "2", "--prompt-len", "8",
-           "--max-tokens", "3", "--no-graphs", "--tp-extra-model", "tiny-llama-g8", "--deadline", str(deadline)]
+           "--max-tokens", "3", "--no-graphs", "--full", "--tp-extra-model", "tiny-llama-g8", "--deadline",
+           str(deadline)]
     t0 = time.monotonic()
     r = _run(cmd, REPO, env, timeout=deadline + 120)
     wall = time.monotonic() - t0
