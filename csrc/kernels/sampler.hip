@@ -11,13 +11,13 @@
 //  * sample: argmax over survivors of x/T + Gumbel(u), u = counter-based hash of
 //    (seed, offset, token) -> bit-exact reproducible (see ops/reference.py philox_uniform).
 // Ties at a threshold are kept (threshold semantics), which matches the reference mask.
-#include "common.h"
+#include "sampler_common.h"
 
 using namespace pk;
 
 namespace {
 
-constexpr int kThreads = 1024;
+constexpr int kThreads = kRowThreads;
 
 __device__ __forceinline__ uint32_t fmix32(uint32_t h) {
   h ^= h >> 16;
@@ -39,35 +39,6 @@ __device__ __forceinline__ float uniform01(uint32_t rh, uint32_t idx) {
   return (static_cast<float>(x >> 8) + 0.5f) * (1.0f / 16777216.0f);
 }
 
-__device__ __forceinline__ uint32_t okey(float f) {
-  const uint32_t u = __float_as_uint(f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
-__device__ __forceinline__ float from_okey(uint32_t k) {
-  return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
-}
-
-template <typename T>
-struct Row;
-
-template <>
-struct Row<bf16_t> {
-  static __device__ __forceinline__ void load8(const bf16_t* p, int v, float* out) {
-    unpack8(reinterpret_cast<const u32x4*>(p)[v], out);
-  }
-};
-
-template <>
-struct Row<float> {
-  static __device__ __forceinline__ void load8(const float* p, int v, float* out) {
-    const float4* q = reinterpret_cast<const float4*>(p) + 2 * v;
-    float4 a = q[0], b = q[1];
-    out[0] = a.x; out[1] = a.y; out[2] = a.z; out[3] = a.w;
-    out[4] = b.x; out[5] = b.y; out[6] = b.z; out[7] = b.w;
-  }
-};
-
 struct Smem {
   float fhist[256];
   uint32_t uhist[256];
@@ -77,49 +48,6 @@ struct Smem {
   uint32_t sel_digit;
   float sel_f;
 };
-
-// Wave 0 finds the digit d (scanning 255 -> 0) where the running total first reaches `need`;
-// returns (d, total of bins above d).  Other waves wait at the barrier.
-template <typename V>
-__device__ __forceinline__ void select_digit(const V* hist, V need, uint32_t* out_digit, V* out_above) {
-  if (threadIdx.x < 64) {
-    const int lane = threadIdx.x;
-    // lane handles bins 255-4*lane .. 252-4*lane (descending)
-    V b[4];
-    V s = 0;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      b[j] = hist[255 - 4 * lane - j];
-      s += b[j];
-    }
-    // inclusive prefix over lanes (descending bins)
-    V incl = s;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      V t = __shfl_up(incl, o, 64);
-      if (lane >= o) incl += t;
-    }
-    const V excl = incl - s;
-    const bool hit = excl < need && incl >= need;
-    const unsigned long long mask = __ballot(hit);
-    const int src = mask ? __ffsll(static_cast<long long>(mask)) - 1 : 63;
-    if (lane == src) {
-      V acc = excl;
-      int d = 252 - 4 * lane;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        if (acc + b[j] >= need) {
-          d = 255 - 4 * lane - j;
-          break;
-        }
-        acc += b[j];
-      }
-      *out_digit = static_cast<uint32_t>(d);
-      *out_above = acc;
-    }
-  }
-  __syncthreads();
-}
 
 template <typename T>
 __global__ void __launch_bounds__(kThreads) sample_kernel(int* __restrict__ out, const T* __restrict__ logits,
@@ -149,42 +77,10 @@ __global__ void __launch_bounds__(kThreads) sample_kernel(int* __restrict__ out,
         besti = 8 * v + j;
       }
   }
-  // block argmax: (value desc, index asc)
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float ov = __shfl_xor(best, o, 64);
-    const int oi = __shfl_xor(besti, o, 64);
-    if (ov > best || (ov == best && oi < besti)) {
-      best = ov;
-      besti = oi;
-    }
-  }
-  if (lane == 0) {
-    sm.red[wid] = best;
-    sm.ired[wid] = besti;
-  }
-  __syncthreads();
-  if (threadIdx.x < 64) {
-    float b = lane < kThreads / 64 ? sm.red[lane] : -INFINITY;
-    int bi = lane < kThreads / 64 ? sm.ired[lane] : 0x7fffffff;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const float ov = __shfl_xor(b, o, 64);
-      const int oi = __shfl_xor(bi, o, 64);
-      if (ov > b || (ov == b && oi < bi)) {
-        b = ov;
-        bi = oi;
-      }
-    }
-    if (lane == 0) {
-      sm.red[0] = b;
-      sm.ired[0] = bi;
-    }
-  }
-  __syncthreads();
-  const float xmax = sm.red[0];
+  block_argmax(best, besti, sm.red, sm.ired);  // (value desc, index asc)
+  const float xmax = best;
   if (!(temp > 0.f)) {
-    if (threadIdx.x == 0) out[row] = sm.ired[0];
+    if (threadIdx.x == 0) out[row] = besti;
     return;
   }
   const float inv_t = 1.f / temp;
@@ -282,35 +178,8 @@ __global__ void __launch_bounds__(kThreads) sample_kernel(int* __restrict__ out,
       }
     }
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float ov = __shfl_xor(bs, o, 64);
-    const int oi = __shfl_xor(bi, o, 64);
-    if (ov > bs || (ov == bs && oi < bi)) {
-      bs = ov;
-      bi = oi;
-    }
-  }
-  __syncthreads();
-  if (lane == 0) {
-    sm.red[wid] = bs;
-    sm.ired[wid] = bi;
-  }
-  __syncthreads();
-  if (threadIdx.x < 64) {
-    float b = lane < kThreads / 64 ? sm.red[lane] : -INFINITY;
-    int bj = lane < kThreads / 64 ? sm.ired[lane] : 0x7fffffff;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const float ov = __shfl_xor(b, o, 64);
-      const int oi = __shfl_xor(bj, o, 64);
-      if (ov > b || (ov == b && oi < bj)) {
-        b = ov;
-        bj = oi;
-      }
-    }
-    if (lane == 0) out[row] = bj;
-  }
+  block_argmax(bs, bi, sm.red, sm.ired);
+  if (threadIdx.x == 0) out[row] = bi;
 }
 
 }  // namespace

@@ -4,7 +4,7 @@ provider layer (``internal/adapters``).
 Registers model tools on the :class:`ToolRouter`:
 
 * ``llm.generate:<model>`` — ``parameters = {prompt | prompt_token_ids, max_tokens, temperature,
-  top_p, top_k, min_p, seed, ignore_eos, stop, stop_token_ids, return: "text"|"struct"}``
+  top_p, top_k, min_p, seed, ignore_eos, stop, stop_token_ids, logprobs, return: "text"|"struct"}``
 * ``llm.chat:<model>``     — same with ``messages = [{role, content}, ...]``, and optionally
   OpenAI ``tools`` / ``tool_choice`` plus ``execute_tools`` / ``tool_secret_id`` /
   ``max_tool_rounds`` (service/tool_calls.py): the struct output then also carries
@@ -14,6 +14,10 @@ Unary ``ExecuteTool`` returns the completion as ``string_output`` (what the refe
 client logs), or a ``struct_output`` ``{text, finish_reason, usage, metrics}`` when
 ``return == "struct"``.  ``ExecuteToolStream`` yields ``string_output`` deltas (tokens that
 arrived together are coalesced into one message) and ends with the struct summary.
+``logprobs`` (0..20: the sampled token's log-probability plus that many top alternatives, from
+the raw logits) adds ``logprobs: {token_ids, token_logprobs, top_logprobs: [[{id, logprob}]]}``
+to the struct summary, one entry per generated token (not cut at a stop string); a request
+that does not ask for the struct still gets the plain string.
 """
 from __future__ import annotations
 
@@ -23,6 +27,7 @@ from typing import Dict, List, Optional
 from .. import proto
 from ..engine.sequence import SamplingParams
 from ..engine.tokenizer import IncrementalDetokenizer
+from ..service import logprob_format as lpf
 from ..service.base import RequestContext, ToolError, ok_status
 from ..service.tool_calls import run_chat, tool_rounds, validate_tools
 
@@ -65,7 +70,8 @@ class LLMTool:
             raise ToolError("INVALID_ARGUMENT", str(e))
         return sp
 
-    def _summary(self, text: str, n_prompt: int, toks: List[int], last, t0: float, with_ids: bool = False) -> dict:
+    def _summary(self, text: str, n_prompt: int, toks: List[int], last, t0: float, with_ids: bool = False,
+                 lps: Optional[list] = None) -> dict:
         m = (last.metrics or {}) if last is not None else {}
         out = {
             "model": self.model_name,
@@ -80,6 +86,8 @@ class LLMTool:
         }
         if with_ids:  # parameters.return_token_ids: the generated ids themselves (token-level clients, tests)
             out["token_ids"] = list(toks)
+        if lps is not None:
+            out["logprobs"] = lpf.struct_block(toks, lps)
         return out
 
     @staticmethod
@@ -106,6 +114,8 @@ class LLMTool:
         if not isinstance(msgs, list) or not msgs:
             raise ToolError("INVALID_ARGUMENT", "llm.chat requires a non-empty 'messages' list")
         sp = self._sampling(params)
+        if sp.logprobs is not None:
+            raise ToolError("INVALID_ARGUMENT", "'logprobs' cannot be combined with function tools")
         try:
             rounds = tool_rounds(params.get("max_tool_rounds"))
         except ValueError as e:
@@ -135,12 +145,15 @@ class LLMTool:
         prompt = self._prompt(params)
         sp = self._sampling(params)
         toks: List[int] = []
+        lps: Optional[list] = [] if sp.logprobs is not None else None
         last = None
         text = ""
         # without stop strings a unary call needs only the final result: a remote engine
         # (engine/remote.py) then reports the request once instead of once per step
         async for out in self.llm.generate(prompt, sp, request_id=ctx.request_id, final_only=not sp.stop):
             toks.extend(out.new_token_ids)
+            if lps is not None:
+                lps.extend(out.logprobs or [])
             last = out
             if sp.stop:
                 text = self.tok.decode(toks)
@@ -152,7 +165,8 @@ class LLMTool:
             text = self.tok.decode(toks)
         resp = proto.ExecuteToolResponse(status=_status())
         if params.get("return") == "struct":
-            resp.struct_output.update(self._summary(text, len(prompt), toks, last, t0, bool(params.get("return_token_ids"))))
+            resp.struct_output.update(self._summary(text, len(prompt), toks, last, t0,
+                                                    bool(params.get("return_token_ids")), lps))
         else:
             resp.string_output = text
         return resp
@@ -166,12 +180,15 @@ class LLMTool:
         prompt = self._prompt(params)
         sp = self._sampling(params)
         toks: List[int] = []
+        lps: Optional[list] = [] if sp.logprobs is not None else None
         last = None
         detok = IncrementalDetokenizer(self.tok)
         agen = self.llm.generate(prompt, sp, request_id=ctx.request_id)
         try:
             async for out in agen:
                 toks.extend(out.new_token_ids)
+                if lps is not None:
+                    lps.extend(out.logprobs or [])
                 last = out
                 before = len(detok.text)
                 delta = detok.push(out.new_token_ids)
@@ -191,7 +208,8 @@ class LLMTool:
             await agen.aclose()
         text = detok.text
         final = proto.ExecuteToolResponse(status=_status())
-        final.struct_output.update(self._summary(text, len(prompt), toks, last, t0, bool(params.get("return_token_ids"))))
+        final.struct_output.update(self._summary(text, len(prompt), toks, last, t0,
+                                                 bool(params.get("return_token_ids")), lps))
         yield final
 
 

@@ -10,6 +10,15 @@ to the gateway's own tools and continue the chat), ``tool_secret_id`` and ``max_
 SSE stream carries the content or the calls in one delta.
 Requests are served by the same :class:`ToolRouter` model tools as gRPC, so both fronts share
 one continuous-batching engine; ``model`` selects the backend like ``llm.chat:<model>``.
+
+Log-probabilities: chat accepts ``logprobs: true`` with ``top_logprobs: 0..20`` and answers with
+``choices[0].logprobs.content``; completions accept ``logprobs: 0..20`` and answer with
+``{tokens, token_logprobs, top_logprobs, text_offset}``.  They come from the raw logits (before
+temperature / top-k / top-p / min-p) and cover every token the engine generated: they are NOT
+cut at a stop string, so they may describe a few tokens past the returned text.  Streamed chunks
+carry the entries of the tokens that arrived with them (also when the detokenizer holds the text
+back and the chunk's content is ``""``).  Non-finite values are sent as ``-9999.0``.  Logprobs
+cannot be combined with function tools (400).
 """
 
 
@@ -20,6 +29,7 @@ import uuid
 from typing import Any, Dict, List, Optional
 
 from ..engine.sequence import SamplingParams
+from ..service import logprob_format as lpf
 from ..service.base import ToolError
 from ..service.tool_calls import run_chat, tool_rounds, validate_tools
 
@@ -45,8 +55,9 @@ def _llm(router, model: Optional[str]):
     return tool.llm, tool.model_name
 
 
-def _params(body: Dict[str, Any]) -> SamplingParams:
+def _params(body: Dict[str, Any], chat: bool = True) -> SamplingParams:
     d = {k: body[k] for k in _SAMPLING_KEYS if k in body and body[k] is not None}
+    d["logprobs"] = lpf.parse_openai(body, chat)
     if "max_completion_tokens" in body and "max_tokens" not in d:
         d["max_tokens"] = body["max_completion_tokens"]
     d.setdefault("max_tokens", 256)
@@ -80,7 +91,7 @@ def create_app(router):
     async def _run(body: Dict[str, Any], chat: bool):
         try:
             llm, model = _llm(router, body.get("model"))
-            sp = _params(body)
+            sp = _params(body, chat)
         except ToolError as e:
             return err(404 if e.code == "NOT_FOUND" else 503, e.message)
         except (ValueError, TypeError) as e:
@@ -95,6 +106,8 @@ def create_app(router):
             except ValueError as e:
                 return err(400, str(e))
             if tools and choice != "none":
+                if sp.logprobs is not None:
+                    return err(400, "'logprobs' cannot be combined with function tools")
                 return await _run_tools(body, llm, model, msgs, sp, tools, choice)
             prompt_ids = tok.encode(tok.apply_chat_template(msgs))
         else:
@@ -116,6 +129,7 @@ def create_app(router):
                 detok = IncrementalDetokenizer(tok)
                 finish = None
                 final_metrics = None
+                offset = 0  # completions: text_offset of the next token
                 if chat:
                     first = {"id": rid, "object": "chat.completion.chunk", "created": created, "model": model,
                              "choices": [{"index": 0, "delta": {"role": "assistant"}, "finish_reason": None}]}
@@ -127,9 +141,18 @@ def create_app(router):
                         finish = out.finish_reason
                         final_metrics = out.metrics or final_metrics
                         delta = detok.push(out.new_token_ids)
-                        if delta:
+                        lp = None
+                        if sp.logprobs is not None and out.logprobs:
+                            if chat:
+                                lp = {"content": lpf.chat_content(tok, out.new_token_ids, out.logprobs)}
+                            else:
+                                lp = lpf.completion_block(tok, out.new_token_ids, out.logprobs, offset)
+                                offset += sum(len(t) for t in lp["tokens"])
+                        if delta or lp is not None:
                             choice = ({"index": 0, "delta": {"content": delta}, "finish_reason": None} if chat
                                       else {"index": 0, "text": delta, "finish_reason": None})
+                            if lp is not None:
+                                choice["logprobs"] = lp
                             ch = {"id": rid, "object": obj + (".chunk" if chat else ""), "created": created,
                                   "model": model, "choices": [choice]}
                             yield f"data: {json.dumps(ch)}\n\n"
@@ -154,6 +177,10 @@ def create_app(router):
         choice = ({"index": 0, "message": {"role": "assistant", "content": text},
                    "finish_reason": last.finish_reason if last else None} if chat
                   else {"index": 0, "text": text, "finish_reason": last.finish_reason if last else None})
+        if sp.logprobs is not None:
+            entries = (last.logprobs if last else None) or []
+            choice["logprobs"] = ({"content": lpf.chat_content(tok, toks, entries)} if chat
+                                  else lpf.completion_block(tok, toks, entries))
         return {"id": rid, "object": obj, "created": created, "model": model, "choices": [choice],
                 "usage": _usage(len(prompt_ids), len(toks), last.metrics if last else None)}
 

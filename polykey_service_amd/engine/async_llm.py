@@ -11,6 +11,7 @@ health to NOT_SERVING).
 from __future__ import annotations
 
 import asyncio
+import dataclasses
 import collections
 import contextlib
 import gc
@@ -159,7 +160,8 @@ class AsyncLLM:
                         break
                     item = RequestOutput(item.request_id, item.new_token_ids + nxt.new_token_ids, nxt.finished,
                                          nxt.finish_reason, nxt.num_prompt_tokens, nxt.num_output_tokens,
-                                         nxt.metrics)
+                                         nxt.metrics,
+                                         None if item.logprobs is None else item.logprobs + (nxt.logprobs or []))
                 if isinstance(item, BaseException):
                     finished = True
                     raise item
@@ -177,11 +179,18 @@ class AsyncLLM:
 
     async def generate_all(self, prompt_ids: List[int], params: SamplingParams,
                            request_id: Optional[str] = None) -> Tuple[List[int], RequestOutput]:
+        """→ (all token ids, the last output).  When the request asked for logprobs the returned
+        output's ``logprobs`` holds the entries of every token, not of the last chunk only."""
         toks: List[int] = []
+        lps: Optional[list] = None
         last = None
         async for out in self.generate(prompt_ids, params, request_id):
             toks.extend(out.new_token_ids)
+            if out.logprobs is not None:
+                lps = (lps or []) + out.logprobs
             last = out
+        if last is not None and lps is not None:
+            last = dataclasses.replace(last, logprobs=lps)
         return toks, last
 
     def shutdown(self, timeout: Optional[float] = None) -> None:

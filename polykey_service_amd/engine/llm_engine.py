@@ -17,6 +17,7 @@ import torch
 from .._native.loader import load_extension
 from ..models import build_model
 from ..models.config import ModelConfig, get_config
+from ..ops.sampler import logprob_entry
 from ..parallel.state import ParallelState, get_state
 from .model_runner import ModelRunner, RunnerConfig
 from .scheduler import ScheduledBatch, Scheduler
@@ -304,6 +305,8 @@ class LLMEngine:
 
     def _complete(self, batch, sampling, handle):
         toks = self.runner.fetch(handle)
+        # packed logprob rows in sampling order, fetched only when a sequence of the step asked
+        lp_rows = self.runner.fetch_logprobs(handle) if len(handle) > 4 and handle[4] is not None else None
         now = time.monotonic()
         for s, n in batch.prefills:
             s.num_computed += n
@@ -311,9 +314,11 @@ class LLMEngine:
         for s in batch.decodes:
             s.num_computed += 1
         done = []
-        for s, tok in zip(sampling, toks):
+        for r, (s, tok) in enumerate(zip(sampling, toks)):
             if s.is_finished():  # aborted while its step was in flight
                 continue
+            if s.logprobs is not None:
+                s.logprobs.append(logprob_entry(lp_rows[r], s.params.logprobs))
             reason = s.append_token(tok, now)
             if reason is not None:
                 self.scheduler.finish(s, reason)
@@ -326,7 +331,8 @@ class LLMEngine:
     @staticmethod
     def _outputs(done) -> List[RequestOutput]:
         return [RequestOutput(s.request_id, [tok], reason is not None, reason.value if reason else None,
-                              len(s.prompt_ids), len(s.output_ids), seq_metrics(s) if reason else None)
+                              len(s.prompt_ids), len(s.output_ids), seq_metrics(s) if reason else None,
+                              [s.logprobs[-1]] if s.logprobs is not None else None)
                 for s, tok, reason in done]
 
     def generate(self, prompts: List[List[int]], params: SamplingParams) -> List[List[int]]:

@@ -70,7 +70,8 @@ class _Layout:
         for name, n in (("header", 16), ("input_ids", max_tokens), ("positions", max_tokens), ("slots", max_tokens),
                         ("context_lens", max_seqs), ("cu_q", max_seqs + 1), ("cu_rel", max_seqs + 1), ("sample_idx", max_seqs),
                         ("temperature", max_seqs), ("top_k", max_seqs), ("top_p", max_seqs), ("min_p", max_seqs),
-                        ("seeds", max_seqs), ("offsets", max_seqs), ("block_tables", max_seqs * max_blocks)):
+                        ("seeds", max_seqs), ("offsets", max_seqs), ("logprobs", max_seqs),
+                        ("block_tables", max_seqs * max_blocks)):
             self.sections[name] = (off, n)
             off += (n + 15) // 16 * 16  # 64-byte aligned sections
         self.size = off
@@ -118,6 +119,13 @@ class ModelRunner:
         self.d = {k: self.layout.view(self.dev_buf, k) for k in self.layout.sections}
         self._tok_hosts = [torch.zeros(cfg.max_num_seqs, dtype=torch.int32, pin_memory=pin) for _ in range(2)]
         self._tok_events = [None, None]
+        # per-token logprobs (ops/sampler.py logprobs): one packed record per sampling row, written
+        # by the kernel right after the sampler (inside every decode graph); rows whose request did
+        # not ask (section "logprobs" = -1) cost one early-returning workgroup.  The host copies
+        # pair with _tok_hosts and are fetched only for steps in which some sequence asked.
+        self.lp_dev = torch.zeros((cfg.max_num_seqs, sampler_ops.LOGPROB_WORDS), dtype=torch.int32, device=device)
+        self._lp_hosts = [torch.zeros((cfg.max_num_seqs, sampler_ops.LOGPROB_WORDS), dtype=torch.int32,
+                                      pin_memory=pin) for _ in range(2)]
         self._tok_i = 0
         self.kv_caches: List[Tuple[torch.Tensor, torch.Tensor]] = []
         self.num_blocks = 0
@@ -223,6 +231,8 @@ class ModelRunner:
                               h["block_tables"], self.max_blocks, h["context_lens"], h["cu_q"])
         # sampling rows: hidden-state row index of each sampling sequence
         pos_of = {s.seq_id: int(h["cu_q"][i + 1]) - 1 for i, s in enumerate(seqs)}
+        h["logprobs"][:len(sampling)] = -1  # rows that ask overwrite theirs below
+        want_lp = False
         for r, s in enumerate(sampling):
             p = s.params
             h["sample_idx"][r] = pos_of[s.seq_id]
@@ -232,7 +242,10 @@ class ModelRunner:
             h["min_p"][r] = p.min_p
             h["seeds"][r] = s.seed
             h["offsets"][r] = len(s.output_ids)
-        return T, n
+            if p.logprobs is not None:
+                h["logprobs"][r] = p.logprobs
+                want_lp = True
+        return T, n, want_lp
 
     def _metadata(self, nd: int, n: int, T: int, max_q: int, short: bool = False) -> attn_ops.AttnMetadata:
         """``short``: every decode context is at most ``self.short_ctx`` tokens."""
@@ -275,7 +288,7 @@ class ModelRunner:
         the sampled ids) without waiting for the GPU; :meth:`fetch` returns the ids."""
         self._next_staging()
         sampling = batch.sampling_seqs()
-        T, n = self._pack(batch, sampling)
+        T, n, want_lp = self._pack(batch, sampling)
         nd = len(batch.decodes)
         ns = len(sampling)
         h = self.h
@@ -298,7 +311,7 @@ class ModelRunner:
         h["header"][:9] = (self.MODE_RUN, T, n, nd, ns, max_q, g, short, 0)
         self._publish(max(n, g))
         toks = self._run(T, n, nd, ns, max_q, g, short)
-        return self._handle(toks, ns)
+        return self._handle(toks, ns, want_lp)
 
     def _short(self, g: int, nd: int) -> int:
         """1 when every decode context fits one attention partition: the step replays bucket
@@ -308,23 +321,36 @@ class ModelRunner:
             return 0
         return int(int(self.h["context_lens"][:nd].max()) <= self.short_ctx)
 
-    def _handle(self, toks, ns: int):
+    def _handle(self, toks, ns: int, want_lp: bool = False):
+        """→ (host ids, ns, event, device ids, host logprob rows or None)."""
         self.stats["steps"] += 1
         if ns == 0 or toks is None:
-            return None, 0, None, None
+            return None, 0, None, None, None
         if not toks.is_cuda:
-            return toks, ns, None, None
+            return toks, ns, None, None, (self.lp_dev[:ns].clone() if want_lp else None)
         self._tok_i ^= 1
         host = self._tok_hosts[self._tok_i]
         host[:ns].copy_(toks[:ns], non_blocking=True)
+        lp_host = None
+        if want_lp:
+            lp_host = self._lp_hosts[self._tok_i]
+            lp_host[:ns].copy_(self.lp_dev[:ns], non_blocking=True)
         ev = self._tok_events[self._tok_i]
         if ev is None:
             ev = self._tok_events[self._tok_i] = torch.cuda.Event()
         ev.record(torch.cuda.current_stream(self.device))
-        return host, ns, ev, toks
+        return host, ns, ev, toks, lp_host
+
+    def fetch_logprobs(self, handle):
+        """After :meth:`fetch` of the same handle: the step's packed logprob rows (numpy int32
+        ``[ns, LOGPROB_WORDS]``, a copy) or None when no sequence of the step asked."""
+        lp, ns = handle[4], handle[1]
+        if lp is None or ns == 0:
+            return None
+        return lp[:ns].numpy().copy()
 
     def fetch(self, handle) -> List[int]:
-        toks, ns, ev, _ = handle
+        toks, ns, ev = handle[:3]
         if ev is not None:
             ev.synchronize()
         self._check_comm()
@@ -368,6 +394,8 @@ class ModelRunner:
         T = self.bm.pack_step(sids, ncomp, ones, np.zeros(n, dtype=np.int32), h["input_ids"], h["positions"],
                               h["slots"], h["block_tables"], self.max_blocks, h["context_lens"], h["cu_q"])
         h["sample_idx"][:n] = np.arange(n, dtype=np.int32)
+        h["logprobs"][:n] = -1
+        want_lp = False
         for r, s in enumerate(seqs):
             p = s.params
             h["temperature"][r] = p.temperature
@@ -376,12 +404,15 @@ class ModelRunner:
             h["min_p"][r] = p.min_p
             h["seeds"][r] = s.seed
             h["offsets"][r] = len(s.output_ids) + 1
+            if p.logprobs is not None:
+                h["logprobs"][r] = p.logprobs
+                want_lp = True
         self._pad_decode(n, g)
         short = self._short(g, n)
         h["header"][:9] = (self.MODE_RUN, T, n, n, n, 0, g, short, 1)
         self._publish(max(n, g))
         self.d["input_ids"][:n].copy_(prev[3][:n])  # step k's sampled ids, stream-ordered
-        return self._handle(self._run(T, n, n, n, 0, g, short), n)
+        return self._handle(self._run(T, n, n, n, 0, g, short), n, want_lp)
 
     def _staged_words(self, n_bt_rows: Optional[int]) -> int:
         """int32 words of the staging buffer a step uses: everything up to the used block-table
@@ -542,8 +573,10 @@ class ModelRunner:
         logits = self.model.compute_logits(rows)
         if self.keep_logits or self.debug_logits:
             self.last_logits = logits
-        return sampler_ops.sample(logits, d["temperature"][:ns], d["top_k"][:ns], d["top_p"][:ns],
+        toks = sampler_ops.sample(logits, d["temperature"][:ns], d["top_k"][:ns], d["top_p"][:ns],
                                   d["min_p"][:ns], d["seeds"][:ns], d["offsets"][:ns])
+        sampler_ops.logprobs(logits, toks, d["logprobs"][:ns], self.lp_dev)
+        return toks
 
     # ------------------------------------------------------------------ graphs
     def _graph_bucket(self, nd: int) -> Optional[int]:
@@ -564,6 +597,7 @@ class ModelRunner:
             h["top_k"][nd:g] = 0
             h["top_p"][nd:g] = 1.0
             h["min_p"][nd:g] = 0.0
+            h["logprobs"][nd:g] = -1
 
     def default_graph_sizes(self) -> List[int]:
         if self.cfg.graph_batch_sizes:
@@ -587,6 +621,7 @@ class ModelRunner:
         self.h["slots"][:] = -1
         self.h["context_lens"][: self.cfg.max_num_seqs] = 1
         self.h["top_p"][:] = 1.0
+        self.h["logprobs"][:] = -1
         self.h["sample_idx"][: self.cfg.max_num_seqs] = np.arange(self.cfg.max_num_seqs, dtype=np.int32)
         self.dev_buf.copy_(self.host_buf)
         torch.cuda.synchronize(self.device)
@@ -603,8 +638,10 @@ class ModelRunner:
                 logits = self.model.compute_logits(hidden)
                 if self.debug_logits:
                     self._graph_logits[(g, int(short))] = logits.clone()
-                return sampler_ops.sample(logits, d["temperature"][:g], d["top_k"][:g], d["top_p"][:g],
+                toks = sampler_ops.sample(logits, d["temperature"][:g], d["top_k"][:g], d["top_p"][:g],
                                           d["min_p"][:g], d["seeds"][:g], d["offsets"][:g])
+                sampler_ops.logprobs(logits, toks, d["logprobs"][:g], self.lp_dev)
+                return toks
 
             # warm up on a side stream (allocator + library handles), then capture
             stream.wait_stream(torch.cuda.current_stream(self.device))

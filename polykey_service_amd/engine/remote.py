@@ -83,6 +83,7 @@ class EngineServer:
         self._conns: Dict[int, Tuple[socket.socket, threading.Lock]] = {}
         self._owner: Dict[str, int] = {}   # rid -> connection that submitted it
         self._final: Dict[str, List] = {}  # rid -> tokens so far (final-only requests)
+        self._final_lp: Dict[str, List] = {}  # rid -> their logprob entries so far (when requested)
 
     def _sink(self, items) -> None:
         """Engine thread: one frame per front end with this step's outputs of its requests."""
@@ -92,22 +93,29 @@ class EngineServer:
                 cid = self._owner.get(rid)
                 if isinstance(o, BaseException):
                     self._final.pop(rid, None)
+                    self._final_lp.pop(rid, None)
                     self._owner.pop(rid, None)
-                    per.setdefault(cid, []).append([rid, [], True, "error", 0, 0, None, str(o)])
+                    per.setdefault(cid, []).append([rid, [], True, "error", 0, 0, None, str(o), None])
                     continue
                 acc = self._final.get(rid)
+                lps = o.logprobs
                 if acc is not None:
                     acc.extend(o.new_token_ids)
+                    if lps is not None:
+                        self._final_lp.setdefault(rid, []).extend(lps)
                     if not o.finished:
                         continue
                     del self._final[rid]
                     ids = acc
+                    lps = self._final_lp.pop(rid, None)
                 else:
                     ids = o.new_token_ids
                 if o.finished:
                     self._owner.pop(rid, None)
                 per.setdefault(cid, []).append([rid, list(ids), o.finished, o.finish_reason, o.num_prompt_tokens,
-                                                o.num_output_tokens, o.metrics, None])
+                                                o.num_output_tokens, o.metrics, None,
+                                                None if lps is None else [[lp, [list(t) for t in top]]
+                                                                          for lp, top in lps]])
             conns = {cid: self._conns.get(cid) for cid in per}
         for cid, out in per.items():
             c = conns.get(cid)
@@ -150,6 +158,7 @@ class EngineServer:
                 elif msg["op"] == "abort":
                     with self._lock:
                         self._final.pop(msg["rid"], None)  # the engine reports nothing more for it
+                        self._final_lp.pop(msg["rid"], None)
                         self._owner.pop(msg["rid"], None)
                     self.llm.abort_external(msg["rid"])
         except OSError:
@@ -230,11 +239,15 @@ class RemoteEngine:
                     continue
                 by_loop: Dict[asyncio.AbstractEventLoop, list] = {}
                 with self._lock:
-                    for rid, ids, fin, reason, npr, nout, metrics, err in msg["items"]:
+                    for rid, ids, fin, reason, npr, nout, metrics, err, *rest in msg["items"]:
                         ent = self._streams.get(rid)
                         if ent is None:
                             continue
-                        item = RuntimeError(err) if err else RequestOutput(rid, ids, fin, reason, npr, nout, metrics)
+                        lps = rest[0] if rest else None
+                        if lps is not None:
+                            lps = [(float(lp), [(int(i), float(v)) for i, v in top]) for lp, top in lps]
+                        item = RuntimeError(err) if err else RequestOutput(rid, ids, fin, reason, npr, nout, metrics,
+                                                                           lps)
                         by_loop.setdefault(ent[0], []).append((ent[1], item))
                 for loop, batch in by_loop.items():
                     try:
@@ -298,7 +311,7 @@ class RemoteEngine:
         last = None
         async for out in self.generate(prompt_ids, params, request_id, final_only=True):
             toks.extend(out.new_token_ids)
-            last = out
+            last = out  # final-only: the one output carries every token's logprobs too
         return toks, last
 
     def shutdown(self, timeout: Optional[float] = None) -> None:

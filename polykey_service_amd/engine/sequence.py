@@ -8,6 +8,9 @@ import time
 from typing import List, Optional, Sequence as Seq
 
 
+MAX_LOGPROBS = 20  # longest top_logprobs list (the logprobs kernel's compile-time constant)
+
+
 @dataclasses.dataclass
 class SamplingParams:
     max_tokens: int = 16
@@ -20,6 +23,9 @@ class SamplingParams:
     ignore_eos: bool = False
     stop: Seq[str] = ()           # stop strings (checked on detokenized text)
     cache_salt: Optional[str] = None  # prefix-cache namespace (e.g. a tenant id); None = shared
+    # per-token log-probabilities from the raw logits: None = off, 0 = the sampled token only,
+    # 1..20 = plus that many top alternatives (ops/sampler.py logprobs)
+    logprobs: Optional[int] = None
 
     def validate(self, max_model_len: int) -> None:
         if self.max_tokens < 1:
@@ -32,6 +38,9 @@ class SamplingParams:
             raise ValueError("top_k must be >= 0")
         if not 0 <= self.min_p < 1:
             raise ValueError("min_p must be in [0, 1)")
+        if self.logprobs is not None and (isinstance(self.logprobs, bool) or not isinstance(self.logprobs, int)
+                                          or not 0 <= self.logprobs <= MAX_LOGPROBS):
+            raise ValueError(f"logprobs must be an integer in [0, {MAX_LOGPROBS}]")
 
     @classmethod
     def from_dict(cls, d: dict) -> "SamplingParams":
@@ -53,6 +62,10 @@ class SamplingParams:
                     v = bool(v)
                 elif f.name == "cache_salt":
                     v = str(v)
+                elif f.name == "logprobs":
+                    if isinstance(v, bool) or (isinstance(v, float) and v != int(v)):
+                        raise ValueError(f"logprobs must be an integer in [0, {MAX_LOGPROBS}]")
+                    v = int(v)
                 kw[f.name] = v
         return cls(**kw)
 
@@ -77,7 +90,7 @@ class Sequence:
     __slots__ = ("seq_id", "request_id", "prompt_ids", "output_ids", "params", "status", "num_computed",
                  "arrival", "first_scheduled", "first_token_time", "finish_time", "finish_reason",
                  "num_preemptions", "eos_token_id", "token_times", "user", "num_cached_tokens",
-                 "cache_salt")
+                 "cache_salt", "logprobs")
 
     def __init__(self, request_id: str, prompt_ids: List[int], params: SamplingParams, eos_token_id: int = -1,
                  user=None, cache_salt: Optional[str] = None):
@@ -97,6 +110,8 @@ class Sequence:
         self.num_cached_tokens = 0  # tokens whose KV came from the prefix cache
         self.eos_token_id = eos_token_id
         self.token_times: List[float] = []
+        # one (logprob, [(id, logprob) x n]) per output token; None unless params.logprobs is set
+        self.logprobs: Optional[list] = [] if getattr(params, "logprobs", None) is not None else None
         self.user = user
         # prefix-cache namespace (Scheduler._salt); None = the request's params.cache_salt
         self.cache_salt = cache_salt if cache_salt is not None else getattr(params, "cache_salt", None)
@@ -147,6 +162,8 @@ class RequestOutput:
     num_prompt_tokens: int = 0
     num_output_tokens: int = 0
     metrics: Optional[dict] = None
+    # one (logprob, [(id, logprob) x n]) per entry of new_token_ids when the request asked for them
+    logprobs: Optional[list] = None
 
 
 def seq_metrics(s: Sequence) -> dict:

@@ -265,3 +265,41 @@ def sample(logits: torch.Tensor, temperature, top_k, top_p, min_p, seeds, offset
         score = (row.double() / t + gumbel).masked_fill(~keep, float("-inf"))
         out[b] = int(torch.argmax(score))
     return out
+
+
+def logprobs(logits: torch.Tensor, tokens, n_top, out: torch.Tensor = None) -> torch.Tensor:
+    """Log-probabilities of the sampled token and the top-n list, from the raw logits, in float64.
+
+    Per row: ``lse = max + log(sum(exp(x - max)))``; the sampled token gets ``x[t] - lse``; the
+    top list holds the ``n`` largest entries in the order (value descending, id ascending) --
+    a stable descending sort.  A row whose maximum is -inf reports -inf everywhere.  Output: the
+    kernel's packed int32 ``[B, 41]`` rows ``[logprob | 20 ids | 20 logprobs]`` (fp32 bits); rows
+    with ``n_top < 0`` are left as they are, slots ``n..19`` hold -1 / -inf."""
+    B, V = logits.shape
+    nmax = 20
+    if out is None:
+        out = torch.zeros((B, 1 + 2 * nmax), dtype=torch.int32)
+    if all(int(n) < 0 for n in n_top[:B]):
+        return out
+    x = logits.detach().cpu().double()
+    fl = out.view(torch.float32)
+    ninf = float("-inf")
+    for b in range(B):
+        n = int(n_top[b])
+        if n < 0:
+            continue
+        n = min(n, nmax, V)
+        row = x[b]
+        m = float(row.max())
+        dead = m == ninf
+        lse = ninf if dead else m + float(torch.log(torch.exp(row - m).sum()))
+        t = int(tokens[b])
+        fl[b, 0] = ninf if dead or not 0 <= t < V else float(row[t]) - lse
+        out[b, 1:1 + nmax] = -1
+        fl[b, 1 + nmax:] = ninf
+        if n:
+            vals, idx = torch.sort(row, descending=True, stable=True)
+            out[b, 1:1 + n] = idx[:n].to(torch.int32)
+            if not dead:
+                fl[b, 1 + nmax:1 + nmax + n] = (vals[:n] - lse).float()
+    return out

@@ -4,6 +4,10 @@ Per-row parameters are device tensors so a decode step (logits → tokens) can b
 a HIP graph: ``temperature`` f32 (0 → greedy), ``top_k`` i32 (0 → off), ``top_p`` f32
 (1 → off), ``min_p`` f32 (0 → off), ``seeds`` i32 and ``offsets`` i32 (the per-request
 token index, so a seeded request reproduces regardless of how it was batched).
+
+:func:`logprobs` reports the log-probabilities of what was sampled, from the *raw* logits
+(before temperature / top-k / top-p / min-p): per row one packed record of ``LOGPROB_WORDS``
+32-bit words, ``[logprob | 20 top ids | 20 top logprobs]`` (see :func:`unpack_logprobs`).
 """
 from __future__ import annotations
 
@@ -42,3 +46,41 @@ def greedy(logits: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Te
     native.call("pk_sample", out.data_ptr(), logits.data_ptr(), 0, 0, 0, 0, 0, 0, 0, B, V, logits.stride(0), dtype,
                 native.stream_ptr())
     return out
+
+
+LOGPROB_NMAX = 20                       # longest top list (the kernel's compile-time constant)
+LOGPROB_WORDS = 1 + 2 * LOGPROB_NMAX    # packed int32 words per row
+
+
+def logprobs(logits: torch.Tensor, tokens: torch.Tensor, n_top: torch.Tensor,
+             out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """logits [B, V] (bf16 or fp32), sampled ids int32 [B], ``n_top`` int32 [B] → packed int32
+    ``[B, LOGPROB_WORDS]``.  ``n_top[b]``: -1 leaves row ``b`` of ``out`` untouched, 0 reports the
+    sampled token's logprob only, 1..20 adds the top list in (value descending, id ascending)
+    order; unused list slots hold id -1 / logprob -inf."""
+    B, V = logits.shape
+    if out is None:
+        out = torch.zeros((B, LOGPROB_WORDS), dtype=torch.int32, device=logits.device)
+    assert out.dtype == torch.int32 and out.is_contiguous() and out.shape[0] >= B and out.shape[1] == LOGPROB_WORDS
+    if not logits.is_cuda:
+        return reference.logprobs(logits, tokens, n_top, out)
+    assert logits.stride(-1) == 1 and logits.dtype in (torch.bfloat16, torch.float32)
+    assert tokens.dtype == torch.int32 and n_top.dtype == torch.int32
+    assert tokens.is_contiguous() and n_top.is_contiguous() and tokens.numel() >= B and n_top.numel() >= B
+    dtype = 0 if logits.dtype == torch.bfloat16 else 1
+    native.call("pk_logprobs", out.data_ptr(), logits.data_ptr(), tokens.data_ptr(), n_top.data_ptr(), B, V,
+                logits.stride(0), dtype, native.stream_ptr())
+    return out
+
+
+def unpack_logprobs(packed: torch.Tensor):
+    """Packed rows (on the host) → (logprob f32 [B], top ids i32 [B, 20], top logprobs f32 [B, 20])."""
+    n = LOGPROB_NMAX
+    return packed[:, 0].view(torch.float32), packed[:, 1:1 + n], packed[:, 1 + n:].view(torch.float32)
+
+
+def logprob_entry(row, n: int):
+    """One packed row (numpy int32 [LOGPROB_WORDS]) → ``(logprob, [(id, logprob) × n])``."""
+    f = row.view("float32")
+    k = LOGPROB_NMAX
+    return float(f[0]), [(int(row[1 + j]), float(f[1 + k + j])) for j in range(n) if row[1 + j] >= 0]
