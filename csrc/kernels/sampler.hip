@@ -9,7 +9,8 @@
 //    top-k survivors: finds the smallest logit v* whose upper set holds >= p of the mass.
 //  * min-p: x >= max + log(min_p) (in temperature-scaled logit space).
 //  * sample: argmax over survivors of x/T + Gumbel(u), u = counter-based hash of
-//    (seed, offset, token) -> bit-exact reproducible (see ops/reference.py philox_uniform).
+//    (seed, offset, token) -> bit-exact reproducible (see ops/reference.py philox_uniform);
+//    u never reaches 1 and the draws next to 1 (the likely winners) are accurate (gumbel()).
 // Ties at a threshold are kept (threshold semantics), which matches the reference mask.
 #include "sampler_common.h"
 
@@ -34,9 +35,22 @@ __device__ __forceinline__ uint32_t row_hash(uint32_t seed, uint32_t offset) {
   return fmix32(h);
 }
 
-__device__ __forceinline__ float uniform01(uint32_t rh, uint32_t idx) {
-  const uint32_t x = fmix32(rh ^ (idx * 0xC2B2AE35u));
-  return (static_cast<float>(x >> 8) + 0.5f) * (1.0f / 16777216.0f);
+// Gumbel(0,1) draw -log(-log u) of token idx, u = (h + 0.5) * 2^-24 with h the hash's top 24 bits
+// (ops/reference.py philox_uniform).  h + 0.5 is exact in fp32 only for h < 2^23; above that it
+// rounds to even (by e = +-0.5), u' = fl(h + 0.5) * 2^-24 reaches 1.0f at h = 2^24 - 1 and the
+// draw becomes +inf; next to 1, where the likely winners are, 1 - u' is off by 2^-25, as much as 1 - u itself.
+// The rounding is known exactly, so it is put back to first order:
+//   -log(u) = -log(u' + e * 2^-24) = -log(u') - e * 2^-24 / u' + O((2^-25 / u')^2),  1 / u' ~ 2 - u'
+// (u' >= 1/2 wherever e != 0; the error of 2 - u' is (1 - u')^2, times a term that matters only
+// where 1 - u' is tiny).  At u' = 1 this gives 2^-25 = 1 - u exactly.  __logf is accurate to
+// 2e-7 *relative* on gfx950, also right below 1, so -log(u') loses nothing there.
+__device__ __forceinline__ float gumbel(uint32_t rh, uint32_t idx) {
+  const float hf = static_cast<float>(fmix32(rh ^ (idx * 0xC2B2AE35u)) >> 8);
+  const float a = hf + 0.5f;
+  const float e = 0.5f - (a - hf);  // exact: 0 below 2^23
+  const float u = a * (1.0f / 16777216.0f);
+  const float t = -__logf(u) - (e * (1.0f / 16777216.0f)) * (2.0f - u);
+  return -__logf(t);
 }
 
 struct Smem {
@@ -169,8 +183,7 @@ __global__ void __launch_bounds__(kThreads) sample_kernel(int* __restrict__ out,
       const float s = f[j] * inv_t;
       if (s >= thr) {
         const int idx = 8 * v + j;
-        const float u = uniform01(rh, static_cast<uint32_t>(idx));
-        const float sc = s - __logf(-__logf(u));
+        const float sc = s + gumbel(rh, static_cast<uint32_t>(idx));
         if (sc > bs || (sc == bs && idx < bi)) {
           bs = sc;
           bi = idx;
