@@ -111,7 +111,7 @@ def grouped_gemm(a: torch.Tensor, w: torch.Tensor, offsets: torch.Tensor, max_ro
             and K % 256 == 0):
         return gemm.grouped_linear(a, w, offsets, max_rows, silu, packed=packed)
     out = torch.empty((a.shape[0], n_out), dtype=a.dtype, device=a.device)
-    if a.is_cuda and max_rows <= 64:
+    if a.is_cuda and max_rows <= 64 and N % 32 == 0 and K % 128 == 0:  # what pk_moe_gemm tiles
         native.call("pk_moe_gemm", out.data_ptr(), a.data_ptr(), w.data_ptr(), offsets.data_ptr(), max_rows, N, K,
                     out.stride(0), E_local, 2 if silu else 0, native.stream_ptr())
         return out
