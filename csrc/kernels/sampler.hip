@@ -63,17 +63,15 @@ struct Smem {
   float sel_f;
 };
 
+// One row, T = the row's element type.  The caller's workgroup runs it for exactly one T (the
+// choice is uniform per workgroup), so the bf16 / fp32 rows and the fp32 rows of an alternative
+// buffer (pk_sample_alt) are the same code.
 template <typename T>
-__global__ void __launch_bounds__(kThreads) sample_kernel(int* __restrict__ out, const T* __restrict__ logits,
-                                                          int64_t stride, int V, const float* __restrict__ temperature,
-                                                          const int* __restrict__ top_k, const float* __restrict__ top_p,
-                                                          const float* __restrict__ min_p, const int* __restrict__ seeds,
-                                                          const int* __restrict__ offsets) {
-  __shared__ Smem sm;
-  __shared__ float above_f;
-  __shared__ uint32_t above_u;
-  const int row = blockIdx.x;
-  const T* x = logits + row * stride;
+__device__ __forceinline__ void sample_row(Smem& sm, float& above_f, uint32_t& above_u, int* __restrict__ out,
+                                           const T* __restrict__ x, int row, int V,
+                                           const float* __restrict__ temperature, const int* __restrict__ top_k,
+                                           const float* __restrict__ top_p, const float* __restrict__ min_p,
+                                           const int* __restrict__ seeds, const int* __restrict__ offsets) {
   const int nv = V / 8;
   const float temp = temperature ? temperature[row] : 0.f;
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
@@ -195,6 +193,52 @@ __global__ void __launch_bounds__(kThreads) sample_kernel(int* __restrict__ out,
   if (threadIdx.x == 0) out[row] = bi;
 }
 
+// alt_slots[row] in [0, n_alt): the row is read as fp32 from alt + alt_slots[row] * alt_stride
+// (ops/penalties.py: the penalised copy of the row); every other row, and every row when
+// alt_slots is null, is read from `logits` as before.
+template <typename T>
+__global__ void __launch_bounds__(kThreads) sample_kernel(int* __restrict__ out, const T* __restrict__ logits,
+                                                          int64_t stride, int V, const float* __restrict__ temperature,
+                                                          const int* __restrict__ top_k, const float* __restrict__ top_p,
+                                                          const float* __restrict__ min_p, const int* __restrict__ seeds,
+                                                          const int* __restrict__ offsets, const float* __restrict__ alt,
+                                                          int64_t alt_stride, const int* __restrict__ alt_slots,
+                                                          int n_alt) {
+  __shared__ Smem sm;
+  __shared__ float above_f;
+  __shared__ uint32_t above_u;
+  const int row = blockIdx.x;
+  const int as = alt_slots ? alt_slots[row] : -1;
+  if (as >= 0 && as < n_alt)
+    sample_row<float>(sm, above_f, above_u, out, alt + as * alt_stride, row, V, temperature, top_k, top_p, min_p, seeds,
+                      offsets);
+  else
+    sample_row<T>(sm, above_f, above_u, out, logits + row * stride, row, V, temperature, top_k, top_p, min_p, seeds,
+                  offsets);
+}
+
+int launch_sample(void* out, const void* logits, const void* temperature, const void* top_k, const void* top_p,
+                  const void* min_p, const void* seeds, const void* offsets, int B, int V, int stride, int dtype,
+                  const void* alt, int64_t alt_stride, const void* alt_slots, int n_alt, hipStream_t stream) {
+  if (B <= 0) return 0;
+  if (V % 8 || stride % 8) return -1;
+  if (alt_slots && (!alt || alt_stride % 8 || alt_stride < V || n_alt < 0)) return -1;
+  if (dtype == 0) {
+    sample_kernel<bf16_t><<<B, kThreads, 0, stream>>>(
+        static_cast<int*>(out), static_cast<const bf16_t*>(logits), stride, V, static_cast<const float*>(temperature),
+        static_cast<const int*>(top_k), static_cast<const float*>(top_p), static_cast<const float*>(min_p),
+        static_cast<const int*>(seeds), static_cast<const int*>(offsets), static_cast<const float*>(alt), alt_stride,
+        static_cast<const int*>(alt_slots), n_alt);
+  } else {
+    sample_kernel<float><<<B, kThreads, 0, stream>>>(
+        static_cast<int*>(out), static_cast<const float*>(logits), stride, V, static_cast<const float*>(temperature),
+        static_cast<const int*>(top_k), static_cast<const float*>(top_p), static_cast<const float*>(min_p),
+        static_cast<const int*>(seeds), static_cast<const int*>(offsets), static_cast<const float*>(alt), alt_stride,
+        static_cast<const int*>(alt_slots), n_alt);
+  }
+  return PK_CHECK_LAUNCH();
+}
+
 }  // namespace
 
 // dtype: 0 = bf16 logits, 1 = fp32 logits.  Any of the parameter arrays may be null (defaults:
@@ -202,18 +246,16 @@ __global__ void __launch_bounds__(kThreads) sample_kernel(int* __restrict__ out,
 PK_EXPORT int pk_sample(void* out, const void* logits, const void* temperature, const void* top_k, const void* top_p,
                         const void* min_p, const void* seeds, const void* offsets, void* unused, int B, int V,
                         int stride, int dtype, hipStream_t stream) {
-  if (B <= 0) return 0;
-  if (V % 8 || stride % 8) return -1;
-  if (dtype == 0) {
-    sample_kernel<bf16_t><<<B, kThreads, 0, stream>>>(
-        static_cast<int*>(out), static_cast<const bf16_t*>(logits), stride, V, static_cast<const float*>(temperature),
-        static_cast<const int*>(top_k), static_cast<const float*>(top_p), static_cast<const float*>(min_p),
-        static_cast<const int*>(seeds), static_cast<const int*>(offsets));
-  } else {
-    sample_kernel<float><<<B, kThreads, 0, stream>>>(
-        static_cast<int*>(out), static_cast<const float*>(logits), stride, V, static_cast<const float*>(temperature),
-        static_cast<const int*>(top_k), static_cast<const float*>(top_p), static_cast<const float*>(min_p),
-        static_cast<const int*>(seeds), static_cast<const int*>(offsets));
-  }
-  return PK_CHECK_LAUNCH();
+  return launch_sample(out, logits, temperature, top_k, top_p, min_p, seeds, offsets, B, V, stride, dtype, nullptr, 0,
+                       nullptr, 0, stream);
+}
+
+// pk_sample with an alternative fp32 source per row: alt fp32 [n_alt, alt_stride], alt_slots int[B]
+// (-1 or out of range: the row is read from `logits` exactly as pk_sample does).
+PK_EXPORT int pk_sample_alt(void* out, const void* logits, const void* temperature, const void* top_k,
+                            const void* top_p, const void* min_p, const void* seeds, const void* offsets, int B, int V,
+                            int stride, int dtype, const void* alt, int64_t alt_stride, const void* alt_slots,
+                            int n_alt, hipStream_t stream) {
+  return launch_sample(out, logits, temperature, top_k, top_p, min_p, seeds, offsets, B, V, stride, dtype, alt,
+                       alt_stride, alt_slots, n_alt, stream);
 }

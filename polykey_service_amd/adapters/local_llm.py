@@ -4,7 +4,8 @@ provider layer (``internal/adapters``).
 Registers model tools on the :class:`ToolRouter`:
 
 * ``llm.generate:<model>`` — ``parameters = {prompt | prompt_token_ids, max_tokens, temperature,
-  top_p, top_k, min_p, seed, ignore_eos, stop, stop_token_ids, logprobs, return: "text"|"struct"}``
+  top_p, top_k, min_p, seed, ignore_eos, stop, stop_token_ids, logprobs, repetition_penalty,
+  frequency_penalty, presence_penalty, logit_bias, return: "text"|"struct"}``
 * ``llm.chat:<model>``     — same with ``messages = [{role, content}, ...]``, and optionally
   OpenAI ``tools`` / ``tool_choice`` plus ``execute_tools`` / ``tool_secret_id`` /
   ``max_tool_rounds`` (service/tool_calls.py): the struct output then also carries
@@ -18,6 +19,10 @@ arrived together are coalesced into one message) and ends with the struct summar
 the raw logits) adds ``logprobs: {token_ids, token_logprobs, top_logprobs: [[{id, logprob}]]}``
 to the struct summary, one entry per generated token (not cut at a stop string); a request
 that does not ask for the struct still gets the plain string.
+``repetition_penalty`` (> 0), ``frequency_penalty`` / ``presence_penalty`` (-2..2) and
+``logit_bias`` (a Struct ``{"<token id>": -100..100}``, at most 300 entries) change what is sampled
+(ops/penalties.py); logprobs still describe the raw logits.  Unlike logprobs they may be combined
+with function tools.  A value out of range is ``INVALID_ARGUMENT``.
 """
 from __future__ import annotations
 

@@ -19,6 +19,11 @@ cut at a stop string, so they may describe a few tokens past the returned text. 
 carry the entries of the tokens that arrived with them (also when the detokenizer holds the text
 back and the chunk's content is ``""``).  Non-finite values are sent as ``-9999.0``.  Logprobs
 cannot be combined with function tools (400).
+
+Penalties: ``frequency_penalty`` / ``presence_penalty`` (-2..2), ``repetition_penalty`` (> 0) and
+``logit_bias`` ({token id: -100..100}, at most 300 entries) are applied before sampling
+(ops/penalties.py); out-of-range values are a 400.  They may be combined with function tools, and
+logprobs keep describing the raw logits.
 """
 
 
@@ -34,7 +39,8 @@ from ..service.base import ToolError
 from ..service.tool_calls import run_chat, tool_rounds, validate_tools
 
 _SAMPLING_KEYS = ("max_tokens", "temperature", "top_p", "top_k", "min_p", "seed", "stop", "ignore_eos",
-                  "stop_token_ids", "cache_salt")
+                  "stop_token_ids", "cache_salt", "repetition_penalty", "frequency_penalty", "presence_penalty",
+                  "logit_bias")
 
 
 

@@ -136,6 +136,7 @@ class LLMEngine:
         self.runner.bm = self.bm
         self.scheduler = Scheduler(self.bm, cfg.max_num_seqs, cfg.max_num_batched_tokens, cfg.max_model_len,
                                    policy=cfg.sched_policy, max_decode_stall=cfg.max_decode_stall)
+        self.scheduler.on_free = self.runner.release_penalty_slot
         if cfg.hip_graphs and dev.type == "cuda":
             self.runner.capture_graphs()
         self.step_count = 0
@@ -173,6 +174,8 @@ class LLMEngine:
             raise ValueError("empty prompt")
         if max(prompt_ids) >= self.mcfg.vocab_size or min(prompt_ids) < 0:
             raise ValueError("prompt token id out of range")
+        if any(not 0 <= t < self.mcfg.vocab_size for t, _ in params.logit_bias):
+            raise ValueError("logit_bias token id out of range")
         seq = Sequence(request_id or uuid.uuid4().hex, prompt_ids, params, self.mcfg.eos_token_id, user)
         self.scheduler.add(seq)
         return seq

@@ -36,6 +36,7 @@ import torch
 from ..ops import attention as attn_ops
 from ..ops import gemm
 from ..ops import native
+from ..ops import penalties as pen_ops
 from ..ops import sampler as sampler_ops
 from .scheduler import ScheduledBatch
 from .sequence import Sequence
@@ -70,7 +71,8 @@ class _Layout:
         for name, n in (("header", 16), ("input_ids", max_tokens), ("positions", max_tokens), ("slots", max_tokens),
                         ("context_lens", max_seqs), ("cu_q", max_seqs + 1), ("cu_rel", max_seqs + 1), ("sample_idx", max_seqs),
                         ("temperature", max_seqs), ("top_k", max_seqs), ("top_p", max_seqs), ("min_p", max_seqs),
-                        ("seeds", max_seqs), ("offsets", max_seqs), ("logprobs", max_seqs),
+                        ("seeds", max_seqs), ("offsets", max_seqs), ("pen_slot", max_seqs), ("rep", max_seqs),
+                        ("freq", max_seqs), ("pres", max_seqs), ("logprobs", max_seqs),
                         ("block_tables", max_seqs * max_blocks)):
             self.sections[name] = (off, n)
             off += (n + 15) // 16 * 16  # 64-byte aligned sections
@@ -79,7 +81,7 @@ class _Layout:
     def view(self, buf: torch.Tensor, name: str) -> torch.Tensor:
         off, n = self.sections[name]
         v = buf[off:off + n]
-        if name in ("temperature", "top_p", "min_p"):
+        if name in ("temperature", "top_p", "min_p", "rep", "freq", "pres"):
             v = v.view(torch.float32)
         if name == "block_tables":
             v = v.view(self.max_seqs, self.max_blocks)
@@ -127,6 +129,17 @@ class ModelRunner:
         self._lp_hosts = [torch.zeros((cfg.max_num_seqs, sampler_ops.LOGPROB_WORDS), dtype=torch.int32,
                                       pin_memory=pin) for _ in range(2)]
         self._tok_i = 0
+        # sampling penalties / logit_bias (ops/penalties.py): device-resident token history, one
+        # slot per penalised sequence, allocated before the KV cache is sized.  A sequence gets
+        # its slot the first time it samples (launch) and loses it when the scheduler frees its
+        # blocks (release_penalty_slot).  Invariant: a freed slot may still receive the update of
+        # a discarded in-flight continuation (or of the step that finished its sequence); that is
+        # safe because whoever takes the slot next is seeded with clear = 1 by a launch enqueued
+        # later on the same stream, and nothing reads a slot before its seed.
+        self.pen = pen_ops.PenaltyState(cfg.max_num_seqs, self.mcfg.vocab_size, device)
+        self._pen_slot: Dict[int, int] = {}                       # seq_id -> slot
+        self._pen_free: List[int] = list(range(cfg.max_num_seqs - 1, -1, -1))
+        self._pen_stale: set = set()                              # seq ids to re-seed from host truth
         self.kv_caches: List[Tuple[torch.Tensor, torch.Tensor]] = []
         self.num_blocks = 0
         self.graphs: Dict[int, torch.cuda.CUDAGraph] = {}
@@ -138,7 +151,7 @@ class ModelRunner:
         a0 = model.layers[0].attn
         self.part_o, self.part_ml = attn_ops.decode_workspace(cfg.max_num_seqs, a0.nq, self.max_blocks, self.bs, device,
                                                               kv_heads=a0.nkv)
-        self.stats = {"steps": 0, "graph_steps": 0, "short_graph_steps": 0, "tokens": 0}
+        self.stats = {"steps": 0, "graph_steps": 0, "short_graph_steps": 0, "tokens": 0, "seed_msgs": 0}
         self.keep_logits = False  # tests: keep the last eager step's logits
         self.last_logits = None
         # diagnostics (tools/tp_rehearsal.py): every step's logits, graphed steps included (a copy
@@ -232,10 +245,14 @@ class ModelRunner:
         # sampling rows: hidden-state row index of each sampling sequence
         pos_of = {s.seq_id: int(h["cu_q"][i + 1]) - 1 for i, s in enumerate(seqs)}
         h["logprobs"][:len(sampling)] = -1  # rows that ask overwrite theirs below
+        self._neutral_penalties(len(sampling))
+        pen = self._pen_slot  # empty unless a live sequence is penalised
         want_lp = False
         for r, s in enumerate(sampling):
             p = s.params
             h["sample_idx"][r] = pos_of[s.seq_id]
+            if pen and s.seq_id in pen:
+                self._fill_penalties(r, s)
             h["temperature"][r] = p.temperature
             h["top_k"][r] = p.top_k
             h["top_p"][r] = p.top_p
@@ -246,6 +263,95 @@ class ModelRunner:
                 h["logprobs"][r] = p.logprobs
                 want_lp = True
         return T, n, want_lp
+
+    # ------------------------------------------------------------------ penalties
+    def _neutral_penalties(self, n: int) -> None:
+        """One vectorised neutral write per step; only rows that ask are overwritten.  Slot -1 is
+        the whole neutral state: ``rep`` / ``freq`` / ``pres`` are read for rows with a slot only."""
+        self.h["pen_slot"][:n] = -1
+
+    def _fill_penalties(self, r: int, s: Sequence) -> None:
+        h, p = self.h, s.params
+        h["pen_slot"][r] = self._pen_slot[s.seq_id]
+        h["rep"][r] = p.repetition_penalty
+        h["freq"][r] = p.frequency_penalty
+        h["pres"][r] = p.presence_penalty
+
+    def release_penalty_slot(self, seq: Sequence) -> None:
+        """Scheduler.on_free: the sequence's blocks were freed (finish, abort, preemption)."""
+        slot = self._pen_slot.pop(seq.seq_id, None)
+        self._pen_stale.discard(seq.seq_id)
+        if slot is not None:
+            self._pen_free.append(slot)
+
+    def _seed_penalties(self, sampling: List[Sequence]) -> None:
+        """Before a step is packed: every penalised sampling sequence without a slot (first
+        sampling step, re-admission after a preemption) or with a stale one gets its slot seeded
+        from host truth (prompt ids, generated ids, bias list).  launch() only runs with no step
+        in flight, so ``output_ids`` is exactly G.  Seeds travel as MODE_SEED messages of their
+        own through the staging buffer (TP workers run the same kernel from the same bytes): the
+        id stream in ``input_ids``, the entry table in ``positions``.  A message holds at most
+        one entry per slot (entries of one launch run concurrently); a history that does not
+        fit continues in the next message with clear = 0."""
+        todo = [s for s in sampling if s.params.has_penalties
+                and (s.seq_id not in self._pen_slot or s.seq_id in self._pen_stale)]
+        if not todo:
+            return
+        cap = self.layout.max_tokens
+        max_entries = max(1, cap // pen_ops.ENTRY_WORDS)
+        ids: List[int] = []
+        entries: List[int] = []
+        for s in todo:
+            if s.seq_id not in self._pen_slot:
+                self._pen_slot[s.seq_id] = self._pen_free.pop()  # running <= max_num_seqs: never empty
+            self._pen_stale.discard(s.seq_id)
+            slot = self._pen_slot[s.seq_id]
+            bias = s.params.logit_bias
+            bias_bits = np.asarray([b for _, b in bias], dtype=np.float32).view(np.int32).tolist()
+            ip = io = ib = 0  # consumed prompt ids / generated ids / bias pairs
+            clear = 1
+            while clear or ip < len(s.prompt_ids) or io < len(s.output_ids) or ib < len(bias):
+                room = cap - len(ids)
+                if room < 2 or len(entries) // pen_ops.ENTRY_WORDS >= max_entries:
+                    self._send_seed(ids, entries)
+                    ids, entries = [], []
+                    room = cap
+                n_p = min(len(s.prompt_ids) - ip, room)
+                n_o = min(len(s.output_ids) - io, room - n_p) if ip + n_p == len(s.prompt_ids) else 0
+                n_b = (min(len(bias) - ib, (room - n_p - n_o) // 2)
+                       if ip + n_p == len(s.prompt_ids) and io + n_o == len(s.output_ids) else 0)
+                entries += [slot, len(ids), n_p, n_o, n_b, clear]
+                ids += s.prompt_ids[ip:ip + n_p] + s.output_ids[io:io + n_o]
+                ids += [t for t, _ in bias[ib:ib + n_b]] + bias_bits[ib:ib + n_b]
+                ip, io, ib, clear = ip + n_p, io + n_o, ib + n_b, 0
+                if ip < len(s.prompt_ids) or io < len(s.output_ids) or ib < len(bias):
+                    self._send_seed(ids, entries)  # the rest of this slot goes in the next message
+                    ids, entries = [], []
+        if entries:
+            self._send_seed(ids, entries)
+
+    def _send_seed(self, ids: List[int], entries: List[int]) -> None:
+        self._next_staging()
+        h = self.h
+        ne = len(entries) // pen_ops.ENTRY_WORDS
+        h["input_ids"][:len(ids)] = ids
+        h["positions"][:len(entries)] = entries
+        h["header"][:9] = (self.MODE_SEED, len(ids), ne, 0, 0, 0, 0, 0, 0)
+        off, _ = self.layout.sections["positions"]
+        self._publish_words((off + len(entries) + 3) // 4 * 4)
+        self._run_seed(len(ids), ne)
+
+    def _run_seed(self, n_ids: int, n_entries: int) -> None:
+        pen_ops.seed(self.pen, self.d["positions"], n_entries, self.d["input_ids"], n_ids)
+        self.stats["seed_msgs"] += 1
+
+    def penalty_state(self, seq: Sequence):
+        """Audit read-back (tests): the device's view of ``seq`` as (set of prompt-flagged ids,
+        {id: count among generated tokens}); None when the sequence holds no slot."""
+        slot = self._pen_slot.get(seq.seq_id)
+        if slot is None:
+            return None
+        return pen_ops.read_slot(self.pen, slot)
 
     def _metadata(self, nd: int, n: int, T: int, max_q: int, short: bool = False) -> attn_ops.AttnMetadata:
         """``short``: every decode context is at most ``self.short_ctx`` tokens."""
@@ -268,7 +374,8 @@ class ModelRunner:
     # ----------------------------------------------------------------- execute
     # header words (section "header"): mode, T, n, nd, ns, max_q, graph bucket, short-context graph,
     # continuation (input ids = the previous step's sampled ids, already on the device)
-    MODE_IDLE, MODE_RUN, MODE_STOP = 0, 1, 2
+    # MODE_SEED: header = (mode, id words, entries); seeds penalty slots (_seed_penalties)
+    MODE_IDLE, MODE_RUN, MODE_STOP, MODE_SEED = 0, 1, 2, 3
 
     @torch.inference_mode()
     def execute(self, batch: ScheduledBatch) -> List[int]:
@@ -286,8 +393,9 @@ class ModelRunner:
     def launch(self, batch: ScheduledBatch):
         """Enqueue one step (pack → H2D → graph replay / eager forward → sample → async D2H of
         the sampled ids) without waiting for the GPU; :meth:`fetch` returns the ids."""
-        self._next_staging()
         sampling = batch.sampling_seqs()
+        self._seed_penalties(sampling)
+        self._next_staging()
         T, n, want_lp = self._pack(batch, sampling)
         nd = len(batch.decodes)
         ns = len(sampling)
@@ -395,9 +503,13 @@ class ModelRunner:
                               h["slots"], h["block_tables"], self.max_blocks, h["context_lens"], h["cu_q"])
         h["sample_idx"][:n] = np.arange(n, dtype=np.int32)
         h["logprobs"][:n] = -1
+        self._neutral_penalties(n)
+        pen = self._pen_slot
         want_lp = False
         for r, s in enumerate(seqs):
             p = s.params
+            if pen and s.seq_id in pen:
+                self._fill_penalties(r, s)
             h["temperature"][r] = p.temperature
             h["top_k"][r] = p.top_k
             h["top_p"][r] = p.top_p
@@ -426,7 +538,9 @@ class ModelRunner:
         """Hand the step inputs to the TP workers (shared-memory ring, host to host) and stage
         them on this rank's device.  The wait for a slot is bounded by the collectives' timeout:
         a worker that died (its pid is gone) or stopped consuming fails the step loudly."""
-        n = self._staged_words(n_bt_rows)
+        self._publish_words(self._staged_words(n_bt_rows))
+
+    def _publish_words(self, n: int) -> None:
         if self.channel is not None and self.model.st.tp_rank == 0:
             if not self.channel.publish(self._hnp[self._cur], n * 4, peer_timeout_ms()):
                 dead = self.channel.dead_consumer()
@@ -492,6 +606,11 @@ class ModelRunner:
             mode, T, n, nd, ns, max_q, g, short, cont = (int(v) for v in self.h["header"][:9])
             if mode == self.MODE_STOP:
                 return
+            if mode == self.MODE_SEED:
+                self._stage_local(nbytes // 4)
+                with torch.inference_mode():
+                    self._run_seed(T, n)
+                continue
             if mode != self.MODE_RUN:
                 continue
             self._stage_local(nbytes // 4)
@@ -517,6 +636,9 @@ class ModelRunner:
         gemm.disable_fused()
         gemm.clear_fused_error()
         self.stats["fused_fallbacks"] = self.stats.get("fused_fallbacks", 0) + 1
+        # the failed step and any continuation of it have counted tokens that are discarded: every
+        # live slot is re-seeded from host truth by the next launch that samples its sequence
+        self._pen_stale.update(self._pen_slot)
         if self.graphs:
             sizes = sorted(self.graphs)
             self.graphs.clear()
@@ -573,9 +695,18 @@ class ModelRunner:
         logits = self.model.compute_logits(rows)
         if self.keep_logits or self.debug_logits:
             self.last_logits = logits
+        return self._sample(logits, ns)
+
+    def _sample(self, logits: torch.Tensor, ns: int) -> torch.Tensor:
+        """logits → penalised copy of the rows with a slot → sample (those rows from the copy) →
+        logprobs (from the raw logits) → count the sampled ids.  Eager and inside every graph."""
+        d = self.d
+        pen_out = pen_ops.apply(self.pen, logits, d["pen_slot"], d["rep"], d["freq"], d["pres"])
         toks = sampler_ops.sample(logits, d["temperature"][:ns], d["top_k"][:ns], d["top_p"][:ns],
-                                  d["min_p"][:ns], d["seeds"][:ns], d["offsets"][:ns])
+                                  d["min_p"][:ns], d["seeds"][:ns], d["offsets"][:ns],
+                                  alt=pen_out, alt_slots=d["pen_slot"])
         sampler_ops.logprobs(logits, toks, d["logprobs"][:ns], self.lp_dev)
+        pen_ops.update(self.pen, d["pen_slot"], toks, ns)
         return toks
 
     # ------------------------------------------------------------------ graphs
@@ -598,6 +729,7 @@ class ModelRunner:
             h["top_p"][nd:g] = 1.0
             h["min_p"][nd:g] = 0.0
             h["logprobs"][nd:g] = -1
+            h["pen_slot"][nd:g] = -1
 
     def default_graph_sizes(self) -> List[int]:
         if self.cfg.graph_batch_sizes:
@@ -622,6 +754,7 @@ class ModelRunner:
         self.h["context_lens"][: self.cfg.max_num_seqs] = 1
         self.h["top_p"][:] = 1.0
         self.h["logprobs"][:] = -1
+        self.h["pen_slot"][:] = -1
         self.h["sample_idx"][: self.cfg.max_num_seqs] = np.arange(self.cfg.max_num_seqs, dtype=np.int32)
         self.dev_buf.copy_(self.host_buf)
         torch.cuda.synchronize(self.device)
@@ -638,10 +771,7 @@ class ModelRunner:
                 logits = self.model.compute_logits(hidden)
                 if self.debug_logits:
                     self._graph_logits[(g, int(short))] = logits.clone()
-                toks = sampler_ops.sample(logits, d["temperature"][:g], d["top_k"][:g], d["top_p"][:g],
-                                          d["min_p"][:g], d["seeds"][:g], d["offsets"][:g])
-                sampler_ops.logprobs(logits, toks, d["logprobs"][:g], self.lp_dev)
-                return toks
+                return self._sample(logits, g)
 
             # warm up on a side stream (allocator + library handles), then capture
             stream.wait_stream(torch.cuda.current_stream(self.device))

@@ -60,6 +60,7 @@ def _params_dict(p: SamplingParams) -> dict:
     d = dataclasses.asdict(p)
     d["stop_token_ids"] = list(d["stop_token_ids"])
     d["stop"] = list(d["stop"])
+    d["logit_bias"] = [[int(t), float(b)] for t, b in d["logit_bias"]]  # pairs: msgpack refuses integer map keys
     return d
 
 

@@ -31,7 +31,7 @@ import bisect
 import collections
 import dataclasses
 import time
-from typing import Deque, Dict, List, Optional, Tuple
+from typing import Callable, Deque, Dict, List, Optional, Tuple
 
 import numpy as np
 
@@ -105,6 +105,14 @@ class Scheduler:
         # seq_id -> (chained block hashes, prompt tokens) at admission
         self._hashes: Dict[int, Tuple[np.ndarray, np.ndarray]] = {}
         self.num_cached_tokens = 0  # prompt tokens served from the prefix cache
+        # called with the sequence at every exit that frees its blocks (finish, abort, both
+        # preemption paths): the runner releases per-sequence device state (its penalty slot)
+        self.on_free: Optional[Callable[[Sequence], None]] = None
+
+    def _free(self, seq: Sequence) -> None:
+        self.bm.free_seq(seq.seq_id)
+        if self.on_free is not None:
+            self.on_free(seq)
 
     # --------------------------------------------------------------- queue ops
     def add(self, seq: Sequence) -> None:
@@ -134,7 +142,7 @@ class Scheduler:
                 self.waiting.remove(seq)
             except ValueError:
                 pass
-        self.bm.free_seq(seq.seq_id)
+        self._free(seq)
         self._hashes.pop(seq.seq_id, None)
         seq.status = SeqStatus.FINISHED
         seq.finish_reason = FinishReason.ABORT
@@ -145,7 +153,7 @@ class Scheduler:
         seq.status = SeqStatus.FINISHED
         seq.finish_reason = reason
         seq.finish_time = time.monotonic()
-        self.bm.free_seq(seq.seq_id)
+        self._free(seq)
         self._hashes.pop(seq.seq_id, None)
         self.by_request.pop(seq.request_id, None)
 
@@ -174,7 +182,7 @@ class Scheduler:
     def _unmatch(self, seq: Sequence) -> None:
         """Admission failed after a match: hand the blocks back (they stay cached)."""
         if self.prefix_caching and seq.num_computed and self.bm.has(seq.seq_id):
-            self.bm.free_seq(seq.seq_id)
+            self._free(seq)
             seq.num_computed = 0
 
     def commit_prefix(self, seq: Sequence) -> None:
@@ -191,7 +199,7 @@ class Scheduler:
         if not self.running or self.running[-1] is protect:
             return None
         cand = self.running.pop()
-        self.bm.free_seq(cand.seq_id)
+        self._free(cand)
         cand.num_computed = 0
         cand.status = SeqStatus.WAITING
         cand.num_preemptions += 1
@@ -243,7 +251,7 @@ class Scheduler:
             # could not even fit this sequence alone: preempt it too
             i = self._index(seq)
             self.running.remove(seq)
-            self.bm.free_seq(seq.seq_id)
+            self._free(seq)
             seq.num_computed = 0
             seq.status = SeqStatus.WAITING
             seq.num_preemptions += 1

@@ -4,11 +4,28 @@ from __future__ import annotations
 import dataclasses
 import enum
 import itertools
+import math
 import time
 from typing import List, Optional, Sequence as Seq
 
 
 MAX_LOGPROBS = 20  # longest top_logprobs list (the logprobs kernel's compile-time constant)
+MAX_LOGIT_BIAS = 300  # longest logit_bias list (the penalty kernels' per-slot table, ops/penalties.py)
+
+
+def _norm_logit_bias(v) -> tuple:
+    """dict with string or int keys (the OpenAI / Struct forms) or a list of (id, value) pairs →
+    a tuple of (int id, float value) sorted by id.  Duplicates are kept for ``validate`` to reject."""
+    items = v.items() if isinstance(v, dict) else v
+    out = []
+    try:
+        for k, b in items:
+            if isinstance(k, bool) or isinstance(b, bool) or (isinstance(k, float) and k != int(k)):
+                raise ValueError
+            out.append((int(k), float(b)))
+    except (TypeError, ValueError):
+        raise ValueError("logit_bias must map token ids to numbers") from None
+    return tuple(sorted(out))
 
 
 @dataclasses.dataclass
@@ -26,6 +43,18 @@ class SamplingParams:
     # per-token log-probabilities from the raw logits: None = off, 0 = the sampled token only,
     # 1..20 = plus that many top alternatives (ops/sampler.py logprobs)
     logprobs: Optional[int] = None
+    # penalties, applied to a copy of the logits before sampling (logprobs stay raw), in this
+    # order: repetition (Hugging Face rule over prompt + generated tokens), frequency and presence
+    # (OpenAI rule over generated tokens), logit_bias.  1 / 0 / 0 / () = off.
+    repetition_penalty: float = 1.0
+    frequency_penalty: float = 0.0
+    presence_penalty: float = 0.0
+    logit_bias: Seq = ()          # sorted tuple of (token id, bias) pairs (from_dict also takes a dict)
+
+    @property
+    def has_penalties(self) -> bool:
+        return (self.repetition_penalty != 1.0 or self.frequency_penalty != 0.0 or self.presence_penalty != 0.0
+                or len(self.logit_bias) > 0)
 
     def validate(self, max_model_len: int) -> None:
         if self.max_tokens < 1:
@@ -41,6 +70,24 @@ class SamplingParams:
         if self.logprobs is not None and (isinstance(self.logprobs, bool) or not isinstance(self.logprobs, int)
                                           or not 0 <= self.logprobs <= MAX_LOGPROBS):
             raise ValueError(f"logprobs must be an integer in [0, {MAX_LOGPROBS}]")
+        for name in ("frequency_penalty", "presence_penalty"):
+            v = getattr(self, name)
+            if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v) or not -2 <= v <= 2:
+                raise ValueError(f"{name} must be in [-2, 2]")
+        r = self.repetition_penalty
+        if isinstance(r, bool) or not isinstance(r, (int, float)) or not math.isfinite(r) or not r > 0:
+            raise ValueError("repetition_penalty must be finite and > 0")
+        if self.logit_bias:
+            lb = _norm_logit_bias(self.logit_bias)
+            if len(lb) > MAX_LOGIT_BIAS:
+                raise ValueError(f"logit_bias holds at most {MAX_LOGIT_BIAS} entries")
+            if len({t for t, _ in lb}) != len(lb):
+                raise ValueError("logit_bias token ids must be unique")
+            if any(t < 0 for t, _ in lb):
+                raise ValueError("logit_bias token id out of range")
+            if any(not math.isfinite(b) or not -100 <= b <= 100 for _, b in lb):
+                raise ValueError("logit_bias values must be in [-100, 100]")
+            self.logit_bias = lb
 
     @classmethod
     def from_dict(cls, d: dict) -> "SamplingParams":
@@ -52,6 +99,12 @@ class SamplingParams:
                     v = int(v)
                 elif f.name in ("temperature", "top_p", "min_p"):
                     v = float(v)
+                elif f.name in ("repetition_penalty", "frequency_penalty", "presence_penalty"):
+                    if isinstance(v, (bool, str)):
+                        raise ValueError(f"{f.name} must be a number")
+                    v = float(v)
+                elif f.name == "logit_bias":
+                    v = _norm_logit_bias(v)
                 elif f.name == "seed":
                     v = int(v)
                 elif f.name in ("stop_token_ids",):

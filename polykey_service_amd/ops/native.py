@@ -41,7 +41,11 @@ SIGNATURES = {
     "pk_paged_decode_qkv": [P, P, I32, I32, P, P, P, P, P, P, P, P, P, I32, I32, I32, I32, I32, I32, F32, I32, P],
     "pk_paged_prefill": [P, P, P, P, P, P, P, P, I32, I32, I32, I32, I32, I32, I32, I32, F32, P],
     "pk_sample": [P, P, P, P, P, P, P, P, P, I32, I32, I32, I32, P],
+    "pk_sample_alt": [P, P, P, P, P, P, P, P, I32, I32, I32, I32, P, I64, P, I32, P],
     "pk_logprobs": [P, P, P, P, I32, I32, I32, I32, P],
+    "pk_penalty_seed": [P, I64, P, P, P, P, I32, P, I32, I32, I32, P],
+    "pk_penalty_apply": [P, I64, P, I64, I32, I32, I32, P, I64, P, P, P, P, P, P, P, I32, P],
+    "pk_penalty_update": [P, I64, P, P, I32, I32, I32, P],
     "pk_embedding": [P, P, P, I32, I32, I32, I32, P],
     "pk_moe_topk_softmax": [P, P, P, I32, I32, I32, I32, I32, P],
     "pk_moe_align": [P, P, P, P, I32, I32, I32, I32, P],

@@ -303,3 +303,87 @@ def logprobs(logits: torch.Tensor, tokens, n_top, out: torch.Tensor = None) -> t
             if not dead:
                 fl[b, 1 + nmax:1 + nmax + n] = (vals[:n] - lse).float()
     return out
+
+
+# --------------------------------------------------------------------------- sampling penalties
+# The device state of ops/penalties.py, on the same packed table: counts int16 [n_slots, Vs],
+# bit 15 = token in the prompt, bits 0..14 = occurrences among the generated tokens (saturating).
+PENALTY_MAX_BIAS = 300
+PENALTY_ENTRY_WORDS = 6  # slot, start, n_prompt, n_out, n_bias, clear
+
+
+def _u16(t: torch.Tensor) -> np.ndarray:
+    return t.numpy().view(np.uint16)
+
+
+def penalty_seed(counts, bias_ids, bias_vals, bias_n, entries, ids, V: int) -> None:
+    """Entries ``[n, 6]`` of (slot, start, n_prompt, n_out, n_bias, clear) over the int32 stream
+    ``ids``: prompt flags from ``ids[start:start+n_prompt]``, counts from the next ``n_out``, then
+    ``n_bias`` bias ids and ``n_bias`` fp32 bit patterns.  ``clear`` wipes the slot first; without
+    it the entry appends.  Out-of-range slots, ids and entries that overrun the stream are ignored."""
+    c = _u16(counts)
+    n_slots = c.shape[0]
+    ids = np.asarray(ids, dtype=np.int32).reshape(-1)
+    for e in np.asarray(entries, dtype=np.int64).reshape(-1, PENALTY_ENTRY_WORDS):
+        slot, start, n_p, n_o, n_b, clear = (int(v) for v in e)
+        if not 0 <= slot < n_slots or min(start, n_p, n_o, n_b) < 0 or start + n_p + n_o + 2 * n_b > ids.size:
+            continue
+        if clear:
+            c[slot] = 0
+            bias_n[slot] = 0
+        base = min(max(int(bias_n[slot]), 0), PENALTY_MAX_BIAS)
+        p = ids[start:start + n_p]
+        c[slot, p[(p >= 0) & (p < V)]] |= 0x8000
+        for t in ids[start + n_p:start + n_p + n_o]:
+            if 0 <= t < V and (c[slot, t] & 0x7FFF) != 0x7FFF:
+                c[slot, t] += 1
+        b0 = start + n_p + n_o
+        k = max(0, min(n_b, PENALTY_MAX_BIAS - base))
+        bias_ids[slot, base:base + k] = torch.from_numpy(ids[b0:b0 + k].copy())
+        bias_vals[slot, base:base + k] = torch.from_numpy(ids[b0 + n_b:b0 + n_b + k].copy().view(np.float32))
+        bias_n[slot] = min(base + n_b, PENALTY_MAX_BIAS)
+
+
+def penalty_apply(logits, counts, slots, rep, freq, pres, bias_ids, bias_vals, bias_n, out=None,
+                  dtype=np.float32):
+    """Rows with ``slots[r]`` in range: ``out[slot, :V]`` = the row after repetition (seen tokens:
+    ``x / r`` if ``x > 0`` else ``x * r``), frequency and presence (``x - f * c``, then ``- p``
+    where ``c > 0``) and bias (``+ b``), in that order.  ``dtype=np.float32`` rounds once per
+    operation (what the kernel computes); ``np.float64`` is the unrounded value a derived bound
+    is measured from (then a new float64 ``[n_slots, V]`` array is returned, NaN where untouched).
+    The logits are never written."""
+    B, V = logits.shape
+    c = _u16(counts)
+    n_slots = c.shape[0]
+    x = logits.detach().float().cpu().numpy()
+    if dtype == np.float64:
+        res = np.full((n_slots, V), np.nan, dtype=np.float64)
+    else:
+        res = out.numpy()
+    with np.errstate(invalid="ignore", over="ignore"):
+        for r in range(B):
+            slot = int(slots[r])
+            if not 0 <= slot < n_slots:
+                continue
+            a = x[r].astype(dtype)
+            w = c[slot, :V]
+            rp, f, p = (dtype(float(v[r])) for v in (rep, freq, pres))
+            seen = w != 0
+            a = np.where(seen, np.where(a > 0, a / rp, a * rp), a)
+            cnt = (w & 0x7FFF).astype(dtype)
+            a = np.where(cnt > 0, (a - f * cnt) - p, a)
+            for j in range(min(max(int(bias_n[slot]), 0), PENALTY_MAX_BIAS)):
+                t = int(bias_ids[slot, j])
+                if 0 <= t < V:
+                    a[t] = a[t] + dtype(float(bias_vals[slot, j]))
+            res[slot, :V] = a
+    return res if dtype == np.float64 else out
+
+
+def penalty_update(counts, slots, tokens, V: int) -> None:
+    """``counts[slots[r], tokens[r]]`` += 1 (saturating at 0x7fff, bit 15 kept) for rows with a slot."""
+    c = _u16(counts)
+    for r in range(len(slots)):
+        slot, t = int(slots[r]), int(tokens[r])
+        if 0 <= slot < c.shape[0] and 0 <= t < V and (c[slot, t] & 0x7FFF) != 0x7FFF:
+            c[slot, t] += 1

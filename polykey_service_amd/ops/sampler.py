@@ -20,19 +20,37 @@ from . import native, reference
 
 def sample(logits: torch.Tensor, temperature: torch.Tensor, top_k: torch.Tensor, top_p: torch.Tensor,
            min_p: torch.Tensor, seeds: torch.Tensor, offsets: torch.Tensor,
-           out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """logits [B, V] (bf16 or fp32) → int32 token ids [B]."""
+           out: Optional[torch.Tensor] = None, alt: Optional[torch.Tensor] = None,
+           alt_slots: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """logits [B, V] (bf16 or fp32) → int32 token ids [B].
+
+    ``alt`` fp32 ``[n, >= V]`` with ``alt_slots`` int32 ``[B]``: a row whose ``alt_slots[b]`` is in
+    ``[0, n)`` is sampled from ``alt[alt_slots[b], :V]`` (its penalised copy, ops/penalties.py)
+    instead of ``logits[b]``; every other row is sampled exactly as without them."""
     B, V = logits.shape
+    assert (alt is None) == (alt_slots is None)
     if not logits.is_cuda:
+        if alt is not None:
+            rows = [b for b in range(B) if 0 <= int(alt_slots[b]) < alt.shape[0]]
+            if rows:
+                logits = logits.float().clone()
+                logits[rows] = alt[alt_slots[rows].long(), :V]
         return reference.sample(logits, temperature, top_k, top_p, min_p, seeds, offsets).to(torch.int32)
     assert logits.stride(-1) == 1
     if out is None:
         out = torch.empty(B, dtype=torch.int32, device=logits.device)
     dtype = 0 if logits.dtype == torch.bfloat16 else 1
     assert logits.dtype in (torch.bfloat16, torch.float32)
-    native.call("pk_sample", out.data_ptr(), logits.data_ptr(), temperature.data_ptr(), top_k.data_ptr(),
-                top_p.data_ptr(), min_p.data_ptr(), seeds.data_ptr(), offsets.data_ptr(), 0, B, V,
-                logits.stride(0), dtype, native.stream_ptr())
+    if alt is None:
+        native.call("pk_sample", out.data_ptr(), logits.data_ptr(), temperature.data_ptr(), top_k.data_ptr(),
+                    top_p.data_ptr(), min_p.data_ptr(), seeds.data_ptr(), offsets.data_ptr(), 0, B, V,
+                    logits.stride(0), dtype, native.stream_ptr())
+        return out
+    assert alt.dtype == torch.float32 and alt.dim() == 2 and alt.stride(1) == 1 and alt.stride(0) >= V
+    assert alt_slots.dtype == torch.int32 and alt_slots.is_contiguous() and alt_slots.numel() >= B
+    native.call("pk_sample_alt", out.data_ptr(), logits.data_ptr(), temperature.data_ptr(), top_k.data_ptr(),
+                top_p.data_ptr(), min_p.data_ptr(), seeds.data_ptr(), offsets.data_ptr(), B, V, logits.stride(0),
+                dtype, alt.data_ptr(), alt.stride(0), alt_slots.data_ptr(), alt.shape[0], native.stream_ptr())
     return out
 
 
