@@ -1,4 +1,5 @@
-// Paged attention (decode + varlen causal prefill) for gfx950, head_dim = 128, bf16 KV.
+// Paged attention (decode + varlen causal prefill) for gfx950, head_dim = 128, bf16 KV -- or FP8
+// (e4m3) KV widened to bf16 on the way to the same MFMAs (kv_fp8.h; the *_fp8 entry points).
 //
 // One wave computes 16 "columns" against a stream of 32-key steps with
 // mfma_f32_16x16x32_bf16.  A column is (query row, head): in DECODE the 16 columns are
@@ -23,6 +24,8 @@
 // workgroup that read the same K/V tile hit the CU's L1.
 // Decode splits long contexts into partitions of kPart keys (flash-decoding) and merges them
 // in a second kernel; sequences that fit one partition are finished in place.
+#include <type_traits>
+
 #include "attn_decode.h"
 
 using namespace pk;
@@ -41,15 +44,35 @@ __global__ void __launch_bounds__(64 * NW) paged_decode_kernel(
                                        blockIdx.z, gridDim.z, lds, Flow{});
 }
 
+// the same workgroup body over an FP8 (e4m3) cache: scale2 carries the K scale (kv_fp8.h)
+template <int kPart, int NW, bool FROM_QKV, int SS = 0>
+__global__ void __launch_bounds__(64 * NW) paged_decode_fp8_kernel(
+    bf16_t* __restrict__ out, const bf16_t* __restrict__ q, fp8_t* __restrict__ kc,
+    fp8_t* __restrict__ vc, const int* __restrict__ block_tables, const int* __restrict__ context_lens,
+    float* __restrict__ part_o, float* __restrict__ part_ml, int n_q, int n_kv, int bs,
+    int max_blocks, int q_stride, int out_stride, int n_parts, float scale2, const QkvIn qi, const KvScale ks) {
+  __shared__ DecodeLds<kPart, NW> lds;
+  decode_tile<kPart, NW, FROM_QKV, SS, 0, 0, fp8_t>(out, q, kc, vc, block_tables, context_lens, part_o, part_ml, n_q,
+                                                    n_kv, bs, max_blocks, q_stride, out_stride, n_parts, scale2, qi,
+                                                    blockIdx.x, blockIdx.y, blockIdx.z, gridDim.z, lds, Flow{}, ks);
+}
+
 // ----------------------------------------------------------------------------- prefill
 // grid (max_q_blocks, n_seqs, n_kv * head_groups), block 64*W with W = min(G, 8) waves:
 // wave w = query head h*G + sub*W + w, 16 query tokens per workgroup.  cu_q: query offsets
 // (relative to q/out), ctx: total keys per seq.  At most 8 waves keeps the VGPR cap at 256.
+// CT = fp8_t: an e4m3 cache (scale2 carries the K scale; the one extra argument, the V scale,
+// multiplies 1 / l -- the bf16 kernels take none).  VS is a parameter pack, empty for bf16 and one
+// float for FP8, rather than a plain float argument: the bf16 prefill kernels so keep the argument
+// lists, and with them the code, they had before the cache type became a template parameter.
+__device__ __forceinline__ float only(float x) { return x; }
+
+template <typename CT, typename... VS>
 __global__ void __launch_bounds__(512) paged_prefill_kernel(
-    bf16_t* __restrict__ out, const bf16_t* __restrict__ q, const bf16_t* __restrict__ kc,
-    const bf16_t* __restrict__ vc, const int* __restrict__ block_tables, const int* __restrict__ context_lens,
+    bf16_t* __restrict__ out, const bf16_t* __restrict__ q, const CT* __restrict__ kc,
+    const CT* __restrict__ vc, const int* __restrict__ block_tables, const int* __restrict__ context_lens,
     const int* __restrict__ cu_q, int n_q, int n_kv, int bs, int max_blocks, int q_stride, int out_stride,
-    float scale2) {
+    float scale2, VS... v_scale) {
   const int qb = blockIdx.x, seq = blockIdx.y;
   const int q0 = cu_q[seq], L = cu_q[seq + 1] - q0;
   if (qb * 16 >= L) return;
@@ -69,13 +92,14 @@ __global__ void __launch_bounds__(512) paged_prefill_kernel(
   load_q(qf, q + static_cast<int64_t>(q0 + (valid ? qi : 0)) * q_stride + hq * kHD, valid);
   WaveState st;
   init_state(st);
-  KVFrag fa, fb;
+  KVFrag<CT> fa, fb;
   attend(st, qf, kc + static_cast<int64_t>(h) * bs * kHD, vc + static_cast<int64_t>(h) * kHD * bs,
          static_cast<int64_t>(n_kv) * bs * kHD, block_tables + static_cast<int64_t>(seq) * max_blocks, 0, bs, 0,
          k_end, kStep, ctx, valid ? qpos : -1, scale2, fa, fb);
   const float lsum = col_sum(st.l);
   if (!valid) return;
-  const float inv = lsum > 0.f ? 1.f / lsum : 0.f;
+  float inv = lsum > 0.f ? 1.f / lsum : 0.f;
+  if constexpr (kIsFp8<CT>) inv *= only(v_scale...);
   bf16_t* o = out + static_cast<int64_t>(q0 + qi) * out_stride + hq * kHD;
 #pragma unroll
   for (int dt = 0; dt < 8; ++dt) {
@@ -111,11 +135,16 @@ typedef __attribute__((ext_vector_type(16))) float f32x16;
 
 __device__ __forceinline__ int swap23(int r) { return (r & ~12) | ((r & 4) << 1) | ((r & 8) >> 1); }
 
-template <int G, int NW>
+// CT = fp8_t: an e4m3 cache.  The staged granules are the same 8 elements, loaded as 8 bytes and
+// widened to bf16 between the global load and the LDS store, so LDS and the compute half are
+// those of the bf16 kernel; scale2 carries the K scale and v_scale multiplies 1 / l.
+template <int G, int NW, typename CT, typename... VS>
 __global__ void __launch_bounds__(64 * NW, 2) paged_prefill_mfma32_kernel(
-    bf16_t* __restrict__ out, const bf16_t* __restrict__ q, const bf16_t* __restrict__ kc,
-    const bf16_t* __restrict__ vc, const int* __restrict__ block_tables, const int* __restrict__ context_lens,
-    const int* __restrict__ cu_q, int n_kv, int bs, int max_blocks, int q_stride, int out_stride, float scale2) {
+    bf16_t* __restrict__ out, const bf16_t* __restrict__ q, const CT* __restrict__ kc,
+    const CT* __restrict__ vc, const int* __restrict__ block_tables, const int* __restrict__ context_lens,
+    const int* __restrict__ cu_q, int n_kv, int bs, int max_blocks, int q_stride, int out_stride, float scale2,
+    VS... v_scale) {
+  using Raw = std::conditional_t<kIsFp8<CT>, uint2, u32x4>;  // one staged granule (8 elements) in registers
   __shared__ __attribute__((aligned(16))) bf16_t K_s[2][kKS][kKRow32];
   __shared__ __attribute__((aligned(16))) bf16_t V_s[2][kHD][kVRow32];
   static_assert(NW % G == 0, "a workgroup holds whole GQA groups");
@@ -141,8 +170,8 @@ __global__ void __launch_bounds__(64 * NW, 2) paged_prefill_mfma32_kernel(
   const int wave_steps = (min(ctx, ctx - L + wave_last_q + 1) + kKS - 1) / kKS;
   const int wave_first_pos = ctx - L + qb * kPQ + (w / G) * 32;  // position of the wave's first query
   const int64_t blk_stride = static_cast<int64_t>(n_kv) * bs * kHD;
-  const bf16_t* kch = kc + static_cast<int64_t>(h) * bs * kHD;
-  const bf16_t* vch = vc + static_cast<int64_t>(h) * kHD * bs;
+  const CT* kch = kc + static_cast<int64_t>(h) * bs * kHD;
+  const CT* vch = vc + static_cast<int64_t>(h) * kHD * bs;
   const int* bt = block_tables + static_cast<int64_t>(seq) * max_blocks;
 
   // ---- staging: per step 1024 K granules (16 B = 8 dims of one key) and 1024 V^T granules
@@ -156,7 +185,7 @@ __global__ void __launch_bounds__(64 * NW, 2) paged_prefill_mfma32_kernel(
   const int vdl = (((lane >> 2) & 1) << 2) | ((lane >> 3) & 3) | (((lane >> 5) & 1) << 3);
   const int vkg = lane & 3;
   // granule g = j * 64 NW + tid (j < NJ): 32-token tile g >> 9, wave chunk (g >> 6) & 7 of it
-  u32x4 ks[NJ], vs[NJ];
+  Raw ks[NJ], vs[NJ];
   auto load_tile = [&](int step) {
     const int s0 = min(step, nsteps - 1) * kKS;
 #pragma unroll
@@ -165,9 +194,9 @@ __global__ void __launch_bounds__(64 * NW, 2) paged_prefill_mfma32_kernel(
       const int tok = min(s0 + 32 * i, ((k_end - 1) >> 5) << 5);
       const int64_t base = static_cast<int64_t>(bt[tok / bs]) * blk_stride;
       // K: fragment-native tile of 32 tokens, piece (ch, kpl) (common.h kcache_off)
-      ks[j] = *reinterpret_cast<const u32x4*>(kch + base + (tok % bs) * kHD + ((ch << 6) | kpl) * 8);
+      ks[j] = *reinterpret_cast<const Raw*>(kch + base + (tok % bs) * kHD + ((ch << 6) | kpl) * 8);
       // V: channel 16 ch + vdl, keys 8 vkg .. of the same 32-token tile (common.h vcache_off)
-      vs[j] = *reinterpret_cast<const u32x4*>(vch + base + vcache_off(tok % bs + 8 * vkg, 16 * ch + vdl));
+      vs[j] = *reinterpret_cast<const Raw*>(vch + base + vcache_off(tok % bs + 8 * vkg, 16 * ch + vdl));
     }
   };
   auto store_tile = [&](int buf) {
@@ -177,8 +206,13 @@ __global__ void __launch_bounds__(64 * NW, 2) paged_prefill_mfma32_kernel(
       // invert kcache_off for piece (ch, kpl): lane' = kpl, (t, kk) = ch
       const int kkey = 8 * ((kpl >> 2) & 3) + 4 * (ch >> 2) + (kpl & 3);
       const int kd = 32 * (kpl >> 4) + 8 * (ch & 3);
-      *reinterpret_cast<u32x4*>(&K_s[buf][32 * i + kkey][kd]) = ks[j];
-      *reinterpret_cast<u32x4*>(&V_s[buf][16 * ch + vdl][32 * i + 8 * vkg]) = vs[j];
+      if constexpr (kIsFp8<CT>) {
+        *reinterpret_cast<u32x4*>(&K_s[buf][32 * i + kkey][kd]) = fp8_widen8(ks[j]);
+        *reinterpret_cast<u32x4*>(&V_s[buf][16 * ch + vdl][32 * i + 8 * vkg]) = fp8_widen8(vs[j]);
+      } else {
+        *reinterpret_cast<u32x4*>(&K_s[buf][32 * i + kkey][kd]) = ks[j];
+        *reinterpret_cast<u32x4*>(&V_s[buf][16 * ch + vdl][32 * i + 8 * vkg]) = vs[j];
+      }
     }
   };
 
@@ -287,7 +321,8 @@ __global__ void __launch_bounds__(64 * NW, 2) paged_prefill_mfma32_kernel(
     l_run = __uint_as_float(b[0]) + __uint_as_float(b[1]);
   }
   if (!valid) return;
-  const float inv = l_run > 0.f ? 1.f / l_run : 0.f;
+  float inv = l_run > 0.f ? 1.f / l_run : 0.f;
+  if constexpr (kIsFp8<CT>) inv *= only(v_scale...);
   bf16_t* op = out + static_cast<int64_t>(q0 + qi) * out_stride + hq * kHD + 4 * hh;
 #pragma unroll
   for (int dt = 0; dt < 4; ++dt)
@@ -328,21 +363,36 @@ PK_EXPORT int pk_set_decode_fill(int n) {
   return 0;
 }
 
+// ks: null for a bf16 cache, the two scales of an FP8 (e4m3) cache
 template <int P>
 static int decode_launch_p(void* out, const void* q, const QkvIn& qi, const void* k_cache, const void* v_cache,
                            const void* block_tables, const void* context_lens, void* part_o, void* part_ml,
                            int n_seqs, int n_q, int n_kv, int bs, int max_blocks, int q_stride,
-                           int out_stride, float scale, int max_ctx, hipStream_t stream) {
+                           int out_stride, float scale, int max_ctx, hipStream_t stream, const KvScale* ks) {
   const int n_parts = (max_ctx + P - 1) / P;
   if (n_parts > 1 && (part_o == nullptr || part_ml == nullptr)) return -2;
   // z is capped: a short context leaves the extra z-workgroups idle, and graph capture fixes
   // the grid for max_model_len, so a z of n_parts would launch mostly-empty workgroups
   dim3 grid(n_kv, n_seqs, n_parts < g_decode_z ? n_parts : g_decode_z);
-#define PK_DECODE_ARGS                                                                                            \
-  static_cast<bf16_t*>(out), static_cast<const bf16_t*>(q), static_cast<bf16_t*>(const_cast<void*>(k_cache)),   \
-      static_cast<bf16_t*>(const_cast<void*>(v_cache)), static_cast<const int*>(block_tables),                  \
+#define PK_DECODE_ARGS_T(T, SC)                                                                                   \
+  static_cast<bf16_t*>(out), static_cast<const bf16_t*>(q), static_cast<T*>(const_cast<void*>(k_cache)),         \
+      static_cast<T*>(const_cast<void*>(v_cache)), static_cast<const int*>(block_tables),                        \
       static_cast<const int*>(context_lens), static_cast<float*>(part_o), static_cast<float*>(part_ml),          \
-      n_q, n_kv, bs, max_blocks, q_stride, out_stride, n_parts, scale * kLog2e, qi
+      n_q, n_kv, bs, max_blocks, q_stride, out_stride, n_parts, (SC) * kLog2e, qi
+#define PK_DECODE_ARGS PK_DECODE_ARGS_T(bf16_t, scale)
+#define PK_DECODE_ARGS8 PK_DECODE_ARGS_T(fp8_t, scale * ks->k), *ks
+  if (ks != nullptr) {
+    if (qi.partial != nullptr) {
+      switch (qi.S) {
+        case 2: paged_decode_fp8_kernel<P, kDecodeWaves, true, 2><<<grid, 64 * kDecodeWaves, 0, stream>>>(PK_DECODE_ARGS8); break;
+        case 4: paged_decode_fp8_kernel<P, kDecodeWaves, true, 4><<<grid, 64 * kDecodeWaves, 0, stream>>>(PK_DECODE_ARGS8); break;
+        case 8: paged_decode_fp8_kernel<P, kDecodeWaves, true, 8><<<grid, 64 * kDecodeWaves, 0, stream>>>(PK_DECODE_ARGS8); break;
+        case 16: paged_decode_fp8_kernel<P, kDecodeWaves, true, 16><<<grid, 64 * kDecodeWaves, 0, stream>>>(PK_DECODE_ARGS8); break;
+        default: paged_decode_fp8_kernel<P, kDecodeWaves, true, 0><<<grid, 64 * kDecodeWaves, 0, stream>>>(PK_DECODE_ARGS8); break;
+      }
+    } else
+      paged_decode_fp8_kernel<P, kDecodeWaves, false><<<grid, 64 * kDecodeWaves, 0, stream>>>(PK_DECODE_ARGS8);
+  } else
   // (the K/V prefetch across the slab reduction for launches that leave most CUs idle, PRE,
   // measured slower: profiles/r5_attn_ab4.jsonl)
   if (qi.partial != nullptr) {
@@ -355,7 +405,9 @@ static int decode_launch_p(void* out, const void* q, const QkvIn& qi, const void
     }
   } else
     paged_decode_kernel<P, kDecodeWaves, false><<<grid, 64 * kDecodeWaves, 0, stream>>>(PK_DECODE_ARGS);
+#undef PK_DECODE_ARGS8
 #undef PK_DECODE_ARGS
+#undef PK_DECODE_ARGS_T
   int rc = PK_CHECK_LAUNCH();
   if (rc || n_parts == 1) return rc;
   dim3 g2(n_q, n_seqs);
@@ -370,7 +422,8 @@ static int decode_launch_p(void* out, const void* q, const QkvIn& qi, const void
 static int decode_launch(void* out, const void* q, const QkvIn& qi, const void* k_cache, const void* v_cache,
                          const void* block_tables, const void* context_lens, void* part_o, void* part_ml,
                          int n_seqs, int n_q, int n_kv, int bs, int max_blocks, int q_stride,
-                         int out_stride, float scale, int max_ctx, hipStream_t stream) {
+                         int out_stride, float scale, int max_ctx, hipStream_t stream,
+                         const KvScale* ks = nullptr) {
   if (n_seqs <= 0) return 0;
   if (n_q % n_kv || n_q / n_kv > 16 || bs % 32 || bs <= 0) return -1;  // K tiles: 32 keys
   // max_ctx bounds the contexts of this launch (<= 0: the block-table capacity).  A launch
@@ -379,10 +432,10 @@ static int decode_launch(void* out, const void* q, const QkvIn& qi, const void* 
   if (decode_part(n_seqs, n_kv, max_ctx) == kDecodePartSmall)
     return decode_launch_p<kDecodePartSmall>(out, q, qi, k_cache, v_cache, block_tables, context_lens, part_o, part_ml,
                                              n_seqs, n_q, n_kv, bs, max_blocks, q_stride, out_stride, scale,
-                                             max_ctx, stream);
+                                             max_ctx, stream, ks);
   return decode_launch_p<kDecodePart>(out, q, qi, k_cache, v_cache, block_tables, context_lens, part_o, part_ml,
                                       n_seqs, n_q, n_kv, bs, max_blocks, q_stride, out_stride, scale, max_ctx,
-                                      stream);
+                                      stream, ks);
 }
 
 // max_blocks: block-table row stride; max_ctx: bound on every context of this launch (<= 0: no bound)
@@ -409,6 +462,34 @@ PK_EXPORT int pk_paged_decode_qkv(void* out, const void* partial, int S, int M, 
                        n_seqs, n_q, n_kv, bs, max_blocks, 0, out_stride, scale, max_ctx, stream);
 }
 
+// The two decode entry points over an FP8 (e4m3) cache: the cache pointers address bytes, element
+// offsets are those of the bf16 layout, k_scale / v_scale are the layer's scales (kv_fp8.h).
+PK_EXPORT int pk_paged_decode_fp8(void* out, const void* q, const void* k_cache, const void* v_cache,
+                                  const void* block_tables, const void* context_lens, void* part_o, void* part_ml,
+                                  int n_seqs, int n_q, int n_kv, int bs, int max_blocks, int q_stride,
+                                  int out_stride, float scale, int max_ctx, float k_scale, float v_scale,
+                                  hipStream_t stream) {
+  if (!kv_scales_ok(k_scale, v_scale)) return -1;
+  const QkvIn none{};
+  const KvScale ks{k_scale, v_scale};
+  return decode_launch(out, q, none, k_cache, v_cache, block_tables, context_lens, part_o, part_ml, n_seqs,
+                       n_q, n_kv, bs, max_blocks, q_stride, out_stride, scale, max_ctx, stream, &ks);
+}
+
+PK_EXPORT int pk_paged_decode_qkv_fp8(void* out, const void* partial, int S, int M, const void* positions,
+                                      const void* cos_sin, const void* slots, void* k_cache, void* v_cache,
+                                      const void* block_tables, const void* context_lens, void* part_o,
+                                      void* part_ml, int n_seqs, int n_q, int n_kv, int bs, int max_blocks,
+                                      int out_stride, float scale, int max_ctx, float k_scale, float v_scale,
+                                      hipStream_t stream) {
+  if (partial == nullptr || S < 1 || M < n_seqs || !kv_scales_ok(k_scale, v_scale)) return -1;
+  QkvIn qi{static_cast<const float*>(partial), static_cast<const int*>(positions), static_cast<const float*>(cos_sin),
+           static_cast<const int*>(slots), S, M};
+  const KvScale ks{k_scale, v_scale};
+  return decode_launch(out, nullptr, qi, k_cache, v_cache, block_tables, context_lens, part_o, part_ml,
+                       n_seqs, n_q, n_kv, bs, max_blocks, 0, out_stride, scale, max_ctx, stream, &ks);
+}
+
 int pk_get_decode_z() { return g_decode_z; }  // the fused QKV -> attention launch (decode_fused.hip)
 
 PK_EXPORT int pk_set_decode_z(int z) {
@@ -417,10 +498,12 @@ PK_EXPORT int pk_set_decode_z(int z) {
   return 0;
 }
 
-PK_EXPORT int pk_paged_prefill(void* out, const void* q, const void* k_cache, const void* v_cache,
-                               const void* block_tables, const void* context_lens, const void* cu_q, void* unused,
-                               int n_seqs, int n_q, int n_kv, int bs, int max_blocks, int q_stride, int out_stride,
-                               int max_q_len, float scale, hipStream_t stream) {
+// CT: cache element type; v_scale: none (bf16) or the V scale (FP8, `scale` then carries the K scale)
+template <typename CT, typename... VS>
+static int prefill_launch(void* out, const void* q, const void* k_cache, const void* v_cache,
+                          const void* block_tables, const void* context_lens, const void* cu_q,
+                          int n_seqs, int n_q, int n_kv, int bs, int max_blocks, int q_stride, int out_stride,
+                          int max_q_len, float scale, hipStream_t stream, VS... v_scale) {
   if (n_seqs <= 0 || max_q_len <= 0) return 0;
   if (n_q % n_kv || n_q / n_kv > 16 || bs % 32 || bs <= 0) return -1;  // K tiles: 32 keys
   const int G = n_q / n_kv;
@@ -432,11 +515,11 @@ PK_EXPORT int pk_paged_prefill(void* out, const void* q, const void* k_cache, co
     const int pq = 32 * nw / G;  // queries per workgroup (nw waves: G heads x nw/G 32-query groups)
     const dim3 grid(n_kv, n_seqs, (max_q_len + pq - 1) / pq);
 #define PK_PREFILL_M32(GG, NWW)                                                                                \
-  paged_prefill_mfma32_kernel<GG, NWW><<<grid, 64 * NWW, 0, stream>>>(                                         \
-      static_cast<bf16_t*>(out), static_cast<const bf16_t*>(q), static_cast<const bf16_t*>(k_cache),          \
-      static_cast<const bf16_t*>(v_cache), static_cast<const int*>(block_tables),                              \
+  paged_prefill_mfma32_kernel<GG, NWW, CT><<<grid, 64 * NWW, 0, stream>>>(                                     \
+      static_cast<bf16_t*>(out), static_cast<const bf16_t*>(q), static_cast<const CT*>(k_cache),              \
+      static_cast<const CT*>(v_cache), static_cast<const int*>(block_tables),                                  \
       static_cast<const int*>(context_lens), static_cast<const int*>(cu_q), n_kv, bs, max_blocks, q_stride,    \
-      out_stride, scale * kLog2e)
+      out_stride, scale * kLog2e, v_scale...)
     switch (G * 16 + nw) {
       case 1 * 16 + 4: PK_PREFILL_M32(1, 4); break;
       case 2 * 16 + 4: PK_PREFILL_M32(2, 4); break;
@@ -450,9 +533,28 @@ PK_EXPORT int pk_paged_prefill(void* out, const void* q, const void* k_cache, co
   const int W = G > 8 ? 8 : G;
   if (G % W) return -1;
   dim3 grid((max_q_len + 15) / 16, n_seqs, n_kv * (G / W));
-  paged_prefill_kernel<<<grid, 64 * W, 0, stream>>>(
-      static_cast<bf16_t*>(out), static_cast<const bf16_t*>(q), static_cast<const bf16_t*>(k_cache),
-      static_cast<const bf16_t*>(v_cache), static_cast<const int*>(block_tables), static_cast<const int*>(context_lens),
-      static_cast<const int*>(cu_q), n_q, n_kv, bs, max_blocks, q_stride, out_stride, scale * kLog2e);
+  paged_prefill_kernel<CT><<<grid, 64 * W, 0, stream>>>(
+      static_cast<bf16_t*>(out), static_cast<const bf16_t*>(q), static_cast<const CT*>(k_cache),
+      static_cast<const CT*>(v_cache), static_cast<const int*>(block_tables), static_cast<const int*>(context_lens),
+      static_cast<const int*>(cu_q), n_q, n_kv, bs, max_blocks, q_stride, out_stride, scale * kLog2e, v_scale...);
   return PK_CHECK_LAUNCH();
+}
+
+PK_EXPORT int pk_paged_prefill(void* out, const void* q, const void* k_cache, const void* v_cache,
+                               const void* block_tables, const void* context_lens, const void* cu_q, void* unused,
+                               int n_seqs, int n_q, int n_kv, int bs, int max_blocks, int q_stride, int out_stride,
+                               int max_q_len, float scale, hipStream_t stream) {
+  return prefill_launch<bf16_t>(out, q, k_cache, v_cache, block_tables, context_lens, cu_q, n_seqs, n_q, n_kv, bs,
+                                max_blocks, q_stride, out_stride, max_q_len, scale, stream);
+}
+
+// Prefill over an FP8 (e4m3) cache, every GQA group size of the bf16 entry point.
+PK_EXPORT int pk_paged_prefill_fp8(void* out, const void* q, const void* k_cache, const void* v_cache,
+                                   const void* block_tables, const void* context_lens, const void* cu_q,
+                                   int n_seqs, int n_q, int n_kv, int bs, int max_blocks, int q_stride,
+                                   int out_stride, int max_q_len, float scale, float k_scale, float v_scale,
+                                   hipStream_t stream) {
+  if (!kv_scales_ok(k_scale, v_scale)) return -1;
+  return prefill_launch<fp8_t>(out, q, k_cache, v_cache, block_tables, context_lens, cu_q, n_seqs, n_q, n_kv, bs,
+                               max_blocks, q_stride, out_stride, max_q_len, scale * k_scale, stream, v_scale);
 }

@@ -3,6 +3,7 @@
 #pragma once
 #include "common.h"
 #include "flow.h"
+#include "kv_fp8.h"
 
 using namespace pk;
 
@@ -25,6 +26,8 @@ int g_decode_z = 4;  // max partition workgroups per (seq, kv head) (pk_set_deco
 // K/V stream loads: plain (non-temporal measured slower: in-situ decode step 4.43 vs 4.45 ms,
 // tools/ab_decode.py)
 __device__ __forceinline__ bf16x8_t ldkv(const bf16_t* p) { return ld8(p); }
+// an FP8 cache: the same 8 elements are 8 bytes, kept raw until the MFMA needs them (kv_fp8.h)
+__device__ __forceinline__ uint2 ldkv(const fp8_t* p) { return *reinterpret_cast<const uint2*>(p); }
 
 // 16-byte load of QKV slab floats p..p+3; SC1: handed over in-launch (sc1 buffer load, base < 2 GiB)
 template <bool SC1>
@@ -91,23 +94,36 @@ struct WaveState {
 
 // K/V fragments of one 32-key step (16 B per lane each): K as the A operand of S^T = K Q^T
 // (2 key tiles x 4 head-dim k-steps), V^T as the A operand of O^T += V^T P^T (8 d-tiles).
+template <typename CT = bf16_t>
 struct KVFrag {
   bf16x8_t k[2][4];
   bf16x8_t v[8];
 };
+
+// FP8 cache: the fragments stay packed (8 bytes per lane, half the registers of the set in
+// flight) and are widened to bf16 right before their MFMA (attend_step)
+template <>
+struct KVFrag<fp8_t> {
+  uint2 k[2][4];
+  uint2 v[8];
+};
+
+__device__ __forceinline__ const bf16x8_t& mfma_operand(const bf16x8_t& f) { return f; }
+__device__ __forceinline__ bf16x8_t mfma_operand(const uint2& f) { return __builtin_bit_cast(bf16x8_t, fp8_widen8(f)); }
 
 // bt[i - bt_base] = physical block of logical block i; `lim` bounds the tokens a load may touch
 // (past it the address is clamped, the data never used), so the block lookups stay inside the
 // caller's block-table window.  K comes from the fragment-native cache tile of step s (common.h
 // kcache_off: one contiguous KiB per load instruction); V likewise (common.h vcache_off): lane
 // (r, g) reads keys 8g..8g+7 of channel 16 dt + r, one contiguous KiB per d-tile (ldkv: plain loads).
-__device__ __forceinline__ void load_kv(KVFrag& f, const bf16_t* __restrict__ kc, const bf16_t* __restrict__ vc,
+template <typename CT>
+__device__ __forceinline__ void load_kv(KVFrag<CT>& f, const CT* __restrict__ kc, const CT* __restrict__ vc,
                                         int64_t blk_stride, const int* __restrict__ bt, int bt_base, int bs, int s,
                                         int lim) {
   const int lane = threadIdx.x & 63;
   const int r = lane & 15, g = lane >> 4;
   const int ks = min(s, lim - 1) & ~31;  // the step's 32-key tile (clamped past the end)
-  const bf16_t* kt = kc + bt[ks / bs - bt_base] * blk_stride + (ks % bs) * kHD + 8 * lane;
+  const CT* kt = kc + bt[ks / bs - bt_base] * blk_stride + (ks % bs) * kHD + 8 * lane;
   PK_DEVICE_ASSERT(bt[ks / bs - bt_base] >= 0);
 #pragma unroll
   for (int t = 0; t < 2; ++t)
@@ -116,12 +132,13 @@ __device__ __forceinline__ void load_kv(KVFrag& f, const bf16_t* __restrict__ kc
   int tok0 = s + 8 * g;
   tok0 = min(tok0, ((lim - 1) >> 3) << 3);
   const int blk = bt[tok0 / bs - bt_base];
-  const bf16_t* p = vc + blk * blk_stride + vcache_off(tok0 % bs, r);  // + 512 per 16-channel tile
+  const CT* p = vc + blk * blk_stride + vcache_off(tok0 % bs, r);  // + 512 per 16-channel tile
 #pragma unroll
   for (int dt = 0; dt < 8; ++dt) f.v[dt] = ldkv(p + dt * 512);
 }
 
-__device__ __forceinline__ void attend_step(WaveState& st, const bf16x8_t (&qf)[4], const KVFrag& f, int s,
+template <typename CT>
+__device__ __forceinline__ void attend_step(WaveState& st, const bf16x8_t (&qf)[4], const KVFrag<CT>& f, int s,
                                             int n_valid, int col_limit, float scale2) {
   const int g = (threadIdx.x & 63) >> 4;
   // ---- S^T = K . Q^T
@@ -130,7 +147,7 @@ __device__ __forceinline__ void attend_step(WaveState& st, const bf16x8_t (&qf)[
   for (int t = 0; t < 2; ++t) {
     acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-    for (int kk = 0; kk < 4; ++kk) acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f.k[t][kk], qf[kk], acc[t], 0, 0, 0);
+    for (int kk = 0; kk < 4; ++kk) acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(mfma_operand(f.k[t][kk]), qf[kk], acc[t], 0, 0, 0);
   }
   // ---- online softmax over this step's 32 keys (8 per lane)
   float sv[8];
@@ -162,7 +179,7 @@ __device__ __forceinline__ void attend_step(WaveState& st, const bf16x8_t (&qf)[
 #pragma unroll
   for (int dt = 0; dt < 8; ++dt) {
     st.o[dt] *= alpha;
-    st.o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f.v[dt], pb, st.o[dt], 0, 0, 0);
+    st.o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(mfma_operand(f.v[dt]), pb, st.o[dt], 0, 0, 0);
   }
 }
 
@@ -172,11 +189,11 @@ __device__ __forceinline__ void attend_step(WaveState& st, const bf16x8_t (&qf)[
 // (loads past the end are clamped to valid addresses and never consumed).
 // PRE = 1 / 2: the caller already loaded the first step / two steps (fa: k_begin, fb: k_begin +
 // k_stride, with the same clamp `lim`), e.g. while it waited for an in-launch hand-off.
-template <int PRE = 0>
-__device__ __forceinline__ void attend(WaveState& st, const bf16x8_t (&qf)[4], const bf16_t* __restrict__ kc,
-                                       const bf16_t* __restrict__ vc, int64_t blk_stride, const int* __restrict__ bt,
+template <int PRE = 0, typename CT = bf16_t>
+__device__ __forceinline__ void attend(WaveState& st, const bf16x8_t (&qf)[4], const CT* __restrict__ kc,
+                                       const CT* __restrict__ vc, int64_t blk_stride, const int* __restrict__ bt,
                                        int bt_base, int bs, int k_begin, int k_end, int k_stride, int n_valid,
-                                       int col_limit, float scale2, KVFrag& fa, KVFrag& fb) {
+                                       int col_limit, float scale2, KVFrag<CT>& fa, KVFrag<CT>& fb) {
   if (k_begin >= k_end) return;
   const int lim = min(n_valid, k_end);
   int s = k_begin;
@@ -246,13 +263,18 @@ struct DecodeLds {
 // before reading them, and read them with sc1 loads.
 // PRE = 1 / 2 (fused launch): the first partition's first one / two K/V steps per wave are
 // requested before the hand-off wait, so they stream in while the QKV tiles finish.
-template <int kPart, int NW, bool FROM_QKV, int SS = 0, int FL = 0, int PRE = 0>
+// CT = fp8_t: an e4m3 cache (kv_fp8.h).  scale2 then carries the K scale, `ks` the two scales: the
+// new token's k / v are quantised as the cache stores them (kn_s / vn_s hold the widened bytes, so
+// the fold path attends to exactly what a later step reads back), and the V scale multiplies the
+// result once, where it is normalised or handed to the merge kernel.
+template <int kPart, int NW, bool FROM_QKV, int SS = 0, int FL = 0, int PRE = 0, typename CT = bf16_t>
 __device__ __forceinline__ void decode_tile(
-    bf16_t* __restrict__ out, const bf16_t* __restrict__ q, bf16_t* __restrict__ kc,
-    bf16_t* __restrict__ vc, const int* __restrict__ block_tables, const int* __restrict__ context_lens,
+    bf16_t* __restrict__ out, const bf16_t* __restrict__ q, CT* __restrict__ kc,
+    CT* __restrict__ vc, const int* __restrict__ block_tables, const int* __restrict__ context_lens,
     float* __restrict__ part_o, float* __restrict__ part_ml, int n_q, int n_kv, int bs,
     int max_blocks, int q_stride, int out_stride, int n_parts, float scale2, const QkvIn qi, const int bx,
-    const int by, const int bz, const int gdz, DecodeLds<kPart, NW>& L, const Flow& fin) {
+    const int by, const int bz, const int gdz, DecodeLds<kPart, NW>& L, const Flow& fin, const KvScale ks = KvScale{}) {
+  constexpr bool kFp8 = kIsFp8<CT>;
   auto& o_lds = L.o_lds;
   auto& ml_lds = L.ml_lds;
   auto& bt_s = L.bt_s;
@@ -309,9 +331,9 @@ __device__ __forceinline__ void decode_tile(
   asm volatile("" : "+v"(ctx), "+v"(pos_q), "+v"(slot_q) :: "memory");
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int64_t blk_stride = static_cast<int64_t>(n_kv) * bs * kHD;
-  const bf16_t* kch = kc + static_cast<int64_t>(h) * bs * kHD;
-  const bf16_t* vch = vc + static_cast<int64_t>(h) * kHD * bs;
-  KVFrag fa, fb;
+  const CT* kch = kc + static_cast<int64_t>(h) * bs * kHD;
+  const CT* vch = vc + static_cast<int64_t>(h) * kHD * bs;
+  KVFrag<CT> fa, fb;
   bool prefetched = false;
   if constexpr (PRE > 0) {
     static_assert(FROM_QKV && kPart % 32 == 0, "prefetch: fused launches, whole 32-key blocks");
@@ -411,6 +433,15 @@ __device__ __forceinline__ void decode_tile(
           ra[e] = x * co[e] - y * si[e];
           rb[e] = y * co[e] + x * si[e];
         }
+        if constexpr (kFp8) {
+          if (it >= G * 16) {  // k: the bf16 GEMM-output rounding, then the cache's (exact in bf16)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+              ra[e] = fp8_round(bf2f(f2bf(ra[e])), ks.k);
+              rb[e] = fp8_round(bf2f(f2bf(rb[e])), ks.k);
+            }
+          }
+        }
         uint2 pa, pb;
         pa.x = pack2(ra[0], ra[1]);
         pa.y = pack2(ra[2], ra[3]);
@@ -422,9 +453,14 @@ __device__ __forceinline__ void decode_tile(
         } else if (fold) {
           dst = &kn_s[j];
         } else {  // fragment-native K tile: 4-dim groups stay contiguous (common.h kcache_off)
-          bf16_t* d = kc + (static_cast<int64_t>(slot / bs) * n_kv + h) * bs * kHD;
-          *reinterpret_cast<uint2*>(d + kcache_off(slot % bs, j)) = pa;
-          *reinterpret_cast<uint2*>(d + kcache_off(slot % bs, j + 64)) = pb;
+          CT* d = kc + (static_cast<int64_t>(slot / bs) * n_kv + h) * bs * kHD;
+          if constexpr (kFp8) {  // ra / rb are cache values already: 4 bytes per group
+            *reinterpret_cast<uint32_t*>(d + kcache_off(slot % bs, j)) = fp8_pack4(ra[0], ra[1], ra[2], ra[3]);
+            *reinterpret_cast<uint32_t*>(d + kcache_off(slot % bs, j + 64)) = fp8_pack4(rb[0], rb[1], rb[2], rb[3]);
+          } else {
+            *reinterpret_cast<uint2*>(d + kcache_off(slot % bs, j)) = pa;
+            *reinterpret_cast<uint2*>(d + kcache_off(slot % bs, j + 64)) = pb;
+          }
           continue;
         }
         *reinterpret_cast<uint2*>(dst) = pa;
@@ -432,16 +468,26 @@ __device__ __forceinline__ void decode_tile(
       } else if (fold) {
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-          vn_s[j + e] = bf2f(f2bf(av[e]));
-          vn_s[j + 64 + e] = bf2f(f2bf(bv[e]));
+          if constexpr (kFp8) {
+            vn_s[j + e] = fp8_round(bf2f(f2bf(av[e])), ks.v);
+            vn_s[j + 64 + e] = fp8_round(bf2f(f2bf(bv[e])), ks.v);
+          } else {
+            vn_s[j + e] = bf2f(f2bf(av[e]));
+            vn_s[j + 64 + e] = bf2f(f2bf(bv[e]));
+          }
         }
       } else {  // transposed V tile: channels j..j+3 are 8 elements apart (common.h vcache_off)
-        bf16_t* d = vc + (static_cast<int64_t>(slot / bs) * n_kv + h) * kHD * bs;
+        CT* d = vc + (static_cast<int64_t>(slot / bs) * n_kv + h) * kHD * bs;
         const int va0 = vcache_off(slot % bs, j), vb0 = vcache_off(slot % bs, j + 64);
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-          d[va0 + 8 * e] = f2bf(av[e]);
-          d[vb0 + 8 * e] = f2bf(bv[e]);
+          if constexpr (kFp8) {
+            d[va0 + 8 * e] = fp8_from(fp8_prep(bf2f(f2bf(av[e])), ks.v));
+            d[vb0 + 8 * e] = fp8_from(fp8_prep(bf2f(f2bf(bv[e])), ks.v));
+          } else {
+            d[va0 + 8 * e] = f2bf(av[e]);
+            d[vb0 + 8 * e] = f2bf(bv[e]);
+          }
         }
       }
     }
@@ -530,6 +576,7 @@ __device__ __forceinline__ void decode_tile(
       L += f;
     }
     const int hq = h * G + c;
+    if constexpr (kFp8) O *= ks.v;  // V scale: once per output element, ahead of 1 / l or the merge
     if (n_eff == 1) {
       out[static_cast<int64_t>(seq) * out_stride + hq * kHD + d] = f2bf(L > 0.f ? O / L : 0.f);
     } else {
@@ -544,11 +591,17 @@ __device__ __forceinline__ void decode_tile(
   if (fold) {  // the new token's row into the paged cache, off the attention's critical path
     const int t = threadIdx.x;
     if (t < kHD) {
-      bf16_t* d = kc + (static_cast<int64_t>(slot / bs) * n_kv + h) * bs * kHD;
-      d[kcache_off(slot % bs, t)] = kn_s[t];
+      CT* d = kc + (static_cast<int64_t>(slot / bs) * n_kv + h) * bs * kHD;
+      if constexpr (kFp8)
+        d[kcache_off(slot % bs, t)] = fp8_from(bf2f(kn_s[t]));  // kn_s / vn_s hold widened cache bytes: exact
+      else
+        d[kcache_off(slot % bs, t)] = kn_s[t];
     } else if (t < 2 * kHD) {
-      bf16_t* d = vc + (static_cast<int64_t>(slot / bs) * n_kv + h) * kHD * bs;
-      d[vcache_off(slot % bs, t - kHD)] = f2bf(vn_s[t - kHD]);
+      CT* d = vc + (static_cast<int64_t>(slot / bs) * n_kv + h) * kHD * bs;
+      if constexpr (kFp8)
+        d[vcache_off(slot % bs, t - kHD)] = fp8_from(vn_s[t - kHD]);
+      else
+        d[vcache_off(slot % bs, t - kHD)] = f2bf(vn_s[t - kHD]);
     }
   }
 }

@@ -6,6 +6,7 @@
 // transposed V cache [block][kv_head][128][block_size].  One workgroup per 32 tokens (below).
 // slot_mapping[t] < 0 marks a padding row: it is rotated but nothing is cached.
 #include "common.h"
+#include "kv_fp8.h"
 
 using namespace pk;
 
@@ -21,12 +22,22 @@ constexpr int kHalf = 64;
 // each lane gathers one (kv head, channel) row across the 32 tokens (coalesced 2-byte loads
 // over the lanes) and writes it as 64 contiguous bytes; other groups fall back to per-token
 // 2-byte stores (the per-element scatter was 85 us for an 8192-token step, 2.6x the bytes' time).
+// CT = fp8_t: an e4m3 cache (kv_fp8.h), one extra argument with the two scales.  q / k are rotated
+// and rounded to bf16 in place as before; the cache gets e4m3(clamp(bf16 value / scale)) at the
+// same element offsets: a lane's 8 k dims are one 8-byte store, a (kv head, channel) row of an
+// aligned 32-token group four 8-byte stores (its 8-key runs are 128 elements apart), any other
+// token single bytes.
 constexpr int kTokTile = 32;
 
+__device__ __forceinline__ KvScale only(KvScale s) { return s; }
+
+// (SC is a pack so that the bf16 kernel keeps its argument list, and with it its code, unchanged:
+// empty for bf16, one KvScale for FP8)
+template <typename CT, typename... SC>
 __global__ void __launch_bounds__(256) rope_and_cache_kernel(bf16_t* __restrict__ qkv, const int* __restrict__ positions,
-                                                             const float* __restrict__ cos_sin, bf16_t* __restrict__ kc,
-                                                             bf16_t* __restrict__ vc, const int* __restrict__ slots,
-                                                             int T, int nq, int nkv, int bs, int q_stride) {
+                                                             const float* __restrict__ cos_sin, CT* __restrict__ kc,
+                                                             CT* __restrict__ vc, const int* __restrict__ slots,
+                                                             int T, int nq, int nkv, int bs, int q_stride, SC... sc) {
   __shared__ int slot_s[kTokTile];
   __shared__ int aligned_s;
   const int t0 = blockIdx.x * kTokTile;
@@ -60,9 +71,22 @@ __global__ void __launch_bounds__(256) rope_and_cache_kernel(bf16_t* __restrict_
     const int slot = slot_s[tt];
     if (head >= nq && slot >= 0) {
       const int kh = head - nq;
-      bf16_t* dst = kc + (static_cast<int64_t>(slot / bs) * nkv + kh) * bs * kHD;  // fragment-native tile
-      *reinterpret_cast<u32x4*>(dst + kcache_off(slot % bs, c)) = va;
-      *reinterpret_cast<u32x4*>(dst + kcache_off(slot % bs, c + kHalf)) = vb;
+      CT* dst = kc + (static_cast<int64_t>(slot / bs) * nkv + kh) * bs * kHD;  // fragment-native tile
+      if constexpr (kIsFp8<CT>) {
+        const float ksc = only(sc...).k;
+        unpack8(va, ra);  // the bf16 values just stored
+        unpack8(vb, rb);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          ra[j] = fp8_prep(ra[j], ksc);
+          rb[j] = fp8_prep(rb[j], ksc);
+        }
+        *reinterpret_cast<uint2*>(dst + kcache_off(slot % bs, c)) = fp8_pack8(ra);
+        *reinterpret_cast<uint2*>(dst + kcache_off(slot % bs, c + kHalf)) = fp8_pack8(rb);
+      } else {
+        *reinterpret_cast<u32x4*>(dst + kcache_off(slot % bs, c)) = va;
+        *reinterpret_cast<u32x4*>(dst + kcache_off(slot % bs, c + kHalf)) = vb;
+      }
     }
   }
   // ---- V
@@ -80,17 +104,29 @@ __global__ void __launch_bounds__(256) rope_and_cache_kernel(bf16_t* __restrict_
     const bf16_t* v0 = qkv + static_cast<int64_t>(t0) * q_stride + voff;
     for (int u = threadIdx.x; u < n_v; u += blockDim.x) {  // u = kv head * 128 + channel
       const int kh = u / kHD, d = u % kHD;
-      uint32_t w[kTokTile / 2];
+      if constexpr (kIsFp8<CT>) {
+        const float vsc = only(sc...).v;
+        CT* vb = vc + (static_cast<int64_t>(blk) * nkv + kh) * kHD * bs;
 #pragma unroll
-      for (int j = 0; j < kTokTile / 2; ++j) {
-        const uint32_t lo = v0[static_cast<int64_t>(2 * j) * q_stride + u];
-        const uint32_t hi = v0[static_cast<int64_t>(2 * j + 1) * q_stride + u];
-        w[j] = lo | (hi << 16);
+        for (int q = 0; q < 4; ++q) {  // 8 keys per 8-byte piece, packed in registers
+          float f[8];
+#pragma unroll
+          for (int j = 0; j < 8; ++j) f[j] = fp8_prep(bf2f(v0[static_cast<int64_t>(8 * q + j) * q_stride + u]), vsc);
+          *reinterpret_cast<uint2*>(vb + vcache_off(k0 + 8 * q, d)) = fp8_pack8(f);
+        }
+      } else {
+        uint32_t w[kTokTile / 2];
+#pragma unroll
+        for (int j = 0; j < kTokTile / 2; ++j) {
+          const uint32_t lo = v0[static_cast<int64_t>(2 * j) * q_stride + u];
+          const uint32_t hi = v0[static_cast<int64_t>(2 * j + 1) * q_stride + u];
+          w[j] = lo | (hi << 16);
+        }
+        CT* vb = vc + (static_cast<int64_t>(blk) * nkv + kh) * kHD * bs;  // 8 keys per 16-byte piece
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+          *reinterpret_cast<u32x4*>(vb + vcache_off(k0 + 8 * q, d)) = u32x4{w[4 * q], w[4 * q + 1], w[4 * q + 2], w[4 * q + 3]};
       }
-      bf16_t* vb = vc + (static_cast<int64_t>(blk) * nkv + kh) * kHD * bs;  // 8 keys per 16-byte piece
-#pragma unroll
-      for (int q = 0; q < 4; ++q)
-        *reinterpret_cast<u32x4*>(vb + vcache_off(k0 + 8 * q, d)) = u32x4{w[4 * q], w[4 * q + 1], w[4 * q + 2], w[4 * q + 3]};
     }
     return;
   }
@@ -99,8 +135,12 @@ __global__ void __launch_bounds__(256) rope_and_cache_kernel(bf16_t* __restrict_
     const int slot = slot_s[tt];
     if (slot < 0) continue;
     const int kh = e / kHD, d = e % kHD;
-    vc[(static_cast<int64_t>(slot / bs) * nkv + kh) * kHD * bs + vcache_off(slot % bs, d)] =
-        qkv[static_cast<int64_t>(t0 + tt) * q_stride + voff + e];
+    if constexpr (kIsFp8<CT>)
+      vc[(static_cast<int64_t>(slot / bs) * nkv + kh) * kHD * bs + vcache_off(slot % bs, d)] =
+          fp8_from(fp8_prep(bf2f(qkv[static_cast<int64_t>(t0 + tt) * q_stride + voff + e]), only(sc...).v));
+    else
+      vc[(static_cast<int64_t>(slot / bs) * nkv + kh) * kHD * bs + vcache_off(slot % bs, d)] =
+          qkv[static_cast<int64_t>(t0 + tt) * q_stride + voff + e];
   }
 }
 
@@ -111,9 +151,23 @@ PK_EXPORT int pk_rope_and_cache(void* qkv, const void* positions, const void* co
                                 int unused, hipStream_t stream) {
   if (T <= 0) return 0;
   if (hd != kHD || (bs % 32) != 0) return -1;  // fragment-native K tiles of 32 tokens
-  rope_and_cache_kernel<<<(T + kTokTile - 1) / kTokTile, 256, 0, stream>>>(
+  rope_and_cache_kernel<bf16_t><<<(T + kTokTile - 1) / kTokTile, 256, 0, stream>>>(
       static_cast<bf16_t*>(qkv), static_cast<const int*>(positions), static_cast<const float*>(cos_sin),
       static_cast<bf16_t*>(k_cache), static_cast<bf16_t*>(v_cache), static_cast<const int*>(slot_mapping), T, nq, nkv,
       bs, q_stride);
+  return PK_CHECK_LAUNCH();
+}
+
+// The same launch writing an FP8 (e4m3) cache: byte = e4m3_rne(clamp(x / scale, -448, 448)).
+PK_EXPORT int pk_rope_and_cache_fp8(void* qkv, const void* positions, const void* cos_sin, void* k_cache, void* v_cache,
+                                    const void* slot_mapping, int T, int nq, int nkv, int hd, int bs, int q_stride,
+                                    float k_scale, float v_scale, hipStream_t stream) {
+  if (T <= 0) return 0;
+  if (hd != kHD || (bs % 32) != 0) return -1;
+  if (!kv_scales_ok(k_scale, v_scale)) return -1;
+  rope_and_cache_kernel<fp8_t><<<(T + kTokTile - 1) / kTokTile, 256, 0, stream>>>(
+      static_cast<bf16_t*>(qkv), static_cast<const int*>(positions), static_cast<const float*>(cos_sin),
+      static_cast<fp8_t*>(k_cache), static_cast<fp8_t*>(v_cache), static_cast<const int*>(slot_mapping), T, nq, nkv,
+      bs, q_stride, KvScale{k_scale, v_scale});
   return PK_CHECK_LAUNCH();
 }

@@ -41,6 +41,7 @@ class ServerConfig:
     kv_block_size: int = 32
     gpu_mem_fraction: float = 0.90
     num_kv_blocks: int = 0         # 0 → size from free HBM
+    kv_cache_dtype: str = "auto"   # auto | bf16 | fp8 (alias fp8_e4m3): KV-cache element type
     hip_graphs: bool = True
     device: str = "cuda"
     seed: int = 0
@@ -75,6 +76,7 @@ _ENV = {
     "kv_block_size": "POLYKEY_KV_BLOCK_SIZE",
     "gpu_mem_fraction": "POLYKEY_GPU_MEM_FRACTION",
     "num_kv_blocks": "POLYKEY_NUM_KV_BLOCKS",
+    "kv_cache_dtype": "POLYKEY_KV_CACHE_DTYPE",
     "hip_graphs": "POLYKEY_HIP_GRAPHS",
     "device": "POLYKEY_DEVICE",
     "seed": "POLYKEY_SEED",
@@ -82,6 +84,20 @@ _ENV = {
     "tls_cert": "POLYKEY_TLS_CERT",
     "tls_key": "POLYKEY_TLS_KEY",
 }
+
+
+KV_CACHE_DTYPES = ("auto", "bf16", "fp8")
+
+
+def normalize_kv_cache_dtype(value: str) -> str:
+    """``--kv-cache-dtype`` / ``POLYKEY_KV_CACHE_DTYPE`` -> "bf16" or "fp8".  "auto" means bf16 and
+    "fp8_e4m3" is an alias of "fp8" (OCP e4m3, per-layer scales); anything else is an error."""
+    v = str(value).strip().lower()
+    if v in ("auto", "bf16"):
+        return "bf16"
+    if v in ("fp8", "fp8_e4m3"):
+        return "fp8"
+    raise ValueError(f"kv_cache_dtype must be one of {', '.join(KV_CACHE_DTYPES)} (got {value!r})")
 
 
 def _flag_name(field: str) -> str:
@@ -124,4 +140,5 @@ def load_server_config(argv: Optional[Sequence[str]] = None,
         except ValueError:
             continue
         setattr(cfg, fname, val)
+    cfg.kv_cache_dtype = normalize_kv_cache_dtype(cfg.kv_cache_dtype)
     return cfg

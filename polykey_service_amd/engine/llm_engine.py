@@ -7,6 +7,7 @@ The async/gRPC face is :mod:`polykey_service_amd.engine.async_llm`.
 from __future__ import annotations
 
 import dataclasses
+import logging
 import os
 import time
 import uuid
@@ -15,6 +16,7 @@ from typing import Callable, Dict, Iterable, List, Optional
 import torch
 
 from .._native.loader import load_extension
+from ..config.server_config import normalize_kv_cache_dtype
 from ..models import build_model
 from ..models.config import ModelConfig, get_config
 from ..ops.sampler import logprob_entry
@@ -39,6 +41,9 @@ class EngineConfig:
     num_kv_blocks: int = 0
     gpu_mem_fraction: float = 0.90
     hip_graphs: bool = True
+    # KV-cache element type: "auto" | "bf16" | "fp8" ("fp8_e4m3"): OCP e4m3 bytes with per-layer
+    # k_scale / v_scale, half the bytes per token (README "KV cache dtype")
+    kv_cache_dtype: str = "auto"
     graph_batch_sizes: tuple = ()
     watermark: float = 0.01
     device: str = ""
@@ -60,7 +65,7 @@ class EngineConfig:
                    block_size=sc.kv_block_size, max_num_seqs=sc.max_num_seqs,
                    max_num_batched_tokens=sc.max_num_batched_tokens, max_model_len=sc.max_model_len,
                    num_kv_blocks=sc.num_kv_blocks, gpu_mem_fraction=sc.gpu_mem_fraction, hip_graphs=sc.hip_graphs,
-                   num_layers=getattr(sc, "num_layers", 0))
+                   num_layers=getattr(sc, "num_layers", 0), kv_cache_dtype=getattr(sc, "kv_cache_dtype", "auto"))
 
 
 def tokenizer_for(cfg: EngineConfig, mcfg: Optional[ModelConfig] = None):
@@ -74,6 +79,7 @@ def tokenizer_for(cfg: EngineConfig, mcfg: Optional[ModelConfig] = None):
 
 class LLMEngine:
     def __init__(self, cfg: EngineConfig, st: Optional[ParallelState] = None, model=None):
+        cfg = dataclasses.replace(cfg, kv_cache_dtype=normalize_kv_cache_dtype(cfg.kv_cache_dtype))
         self.cfg = cfg
         self.st = st or get_state()
         mcfg: ModelConfig = get_config(cfg.model_path or cfg.model)
@@ -127,10 +133,15 @@ class LLMEngine:
         rcfg = RunnerConfig(block_size=cfg.block_size, max_num_seqs=cfg.max_num_seqs,
                             max_num_batched_tokens=cfg.max_num_batched_tokens, max_model_len=cfg.max_model_len,
                             num_kv_blocks=cfg.num_kv_blocks, gpu_mem_fraction=cfg.gpu_mem_fraction,
-                            hip_graphs=cfg.hip_graphs, graph_batch_sizes=tuple(cfg.graph_batch_sizes))
+                            hip_graphs=cfg.hip_graphs, graph_batch_sizes=tuple(cfg.graph_batch_sizes),
+                            kv_cache_dtype=cfg.kv_cache_dtype)
         self.runner = ModelRunner(model, rcfg, dev)
         self._serving_preflight(mcfg)
         nblocks = self.runner.allocate_kv_cache()
+        self.kv_bytes_per_token = self.runner.kv_bytes_per_block() // cfg.block_size
+        logging.getLogger(__name__).info("KV cache: dtype %s, %d bytes per block (%d per token), %d blocks",
+                                         cfg.kv_cache_dtype, self.runner.kv_bytes_per_block(),
+                                         self.kv_bytes_per_token, nblocks)
         rt = load_extension("_pk_runtime")
         self.bm = rt.BlockManager(nblocks, cfg.block_size, int(nblocks * cfg.watermark), cfg.prefix_caching)
         self.runner.bm = self.bm

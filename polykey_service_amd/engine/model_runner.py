@@ -52,6 +52,7 @@ class RunnerConfig:
     gpu_mem_fraction: float = 0.90
     hip_graphs: bool = True
     graph_batch_sizes: Tuple[int, ...] = ()
+    kv_cache_dtype: str = "bf16"     # "bf16" (the model dtype) | "fp8" (OCP e4m3 + per-layer scales)
 
 
 # Long-context decode merges its partitions in a second kernel (an in-kernel last-arriver merge
@@ -187,30 +188,44 @@ class ModelRunner:
             self.channel.unlink()  # nothing left in /dev/shm if the group is killed
 
     # ---------------------------------------------------------------- KV cache
+    def kv_dtype(self) -> torch.dtype:
+        """Element type of the paged caches: the model's, or e4m3 for ``kv_cache_dtype="fp8"``."""
+        if self.cfg.kv_cache_dtype == "fp8":
+            return attn_ops.FP8
+        if self.cfg.kv_cache_dtype not in ("bf16", "auto"):
+            raise ValueError(f"kv_cache_dtype must be one of auto, bf16, fp8 (got {self.cfg.kv_cache_dtype!r})")
+        return self.model.dtype
+
     def kv_bytes_per_block(self) -> int:
         a = self.model.layers[0].attn
-        return 2 * len(self.model.layers) * a.nkv * self.bs * a.hd * 2
+        return 2 * len(self.model.layers) * a.nkv * self.bs * a.hd * self.kv_dtype().itemsize
 
     def allocate_kv_cache(self, num_blocks: int = 0) -> int:
         a = self.model.layers[0].attn
         if num_blocks <= 0:
             num_blocks = self.cfg.num_kv_blocks
         if num_blocks <= 0:
+            # a byte budget: a cache of narrower elements gets that many times the blocks (FP8: 2x)
+            ratio = max(1, self.model.dtype.itemsize // self.kv_dtype().itemsize)
             if self.device.type == "cuda":
                 torch.cuda.synchronize(self.device)
                 free, total = torch.cuda.mem_get_info(self.device)
                 reserve = self.activation_reserve_bytes()
                 usable = free - (1.0 - self.cfg.gpu_mem_fraction) * total - reserve
-                num_blocks = int(max(usable, 0) // self.kv_bytes_per_block())
+                num_blocks = int(max(usable, 0) // (self.kv_bytes_per_block() * ratio))
                 cap = self.cfg.max_num_seqs * self.max_blocks + 16
-                num_blocks = max(16, min(num_blocks, cap))
+                num_blocks = max(16, min(num_blocks, cap)) * ratio
             else:
-                num_blocks = max(16, min(self.cfg.max_num_seqs * self.max_blocks, 4096))
+                num_blocks = max(16, min(self.cfg.max_num_seqs * self.max_blocks, 4096)) * ratio
         self.num_blocks = num_blocks
         self.kv_caches = []
+        dt = self.kv_dtype()
+        # (every TP rank allocates the same dtype: the ranks build their runner from one engine
+        # config; the model routes around its bf16-only launches by the dtype of these tensors)
+        raw = torch.uint8 if dt == attn_ops.FP8 else dt
         for _ in self.model.layers:
-            k = torch.zeros((num_blocks, a.nkv, self.bs, a.hd), dtype=self.model.dtype, device=self.device)
-            v = torch.zeros((num_blocks, a.nkv, a.hd, self.bs), dtype=self.model.dtype, device=self.device)
+            k = torch.zeros((num_blocks, a.nkv, self.bs, a.hd), dtype=raw, device=self.device).view(dt)
+            v = torch.zeros((num_blocks, a.nkv, a.hd, self.bs), dtype=raw, device=self.device).view(dt)
             self.kv_caches.append((k, v))
         return num_blocks
 

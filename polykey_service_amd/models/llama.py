@@ -28,6 +28,7 @@ Vocab-parallel embedding and LM head for TP>1 (logits all-gathered for sampling)
 """
 from __future__ import annotations
 
+import logging
 import math
 import os
 from typing import List, Optional, Tuple
@@ -46,6 +47,7 @@ from ..parallel import comm
 from ..parallel.state import ParallelState, get_state
 from ..utils import test_hooks
 from .config import ModelConfig
+from . import weights
 from .weights import SafetensorsIndex, random_full, random_shard, shard_cols, shard_rows
 
 
@@ -154,6 +156,9 @@ class LlamaAttention(nn.Module):
         # fault injection for the TP correctness tests (LlamaForCausalLM, POLYKEY_FAULT_DROP_PARTIAL):
         # this rank's o-projection input is zeroed, i.e. its partial never reaches the collective
         self.fault_drop = False
+        # FP8 KV cache: attention reads scale * byte (checkpoint k_scale / v_scale, replicated under TP)
+        self.k_scale = 1.0
+        self.v_scale = 1.0
 
     def drop(self, a: torch.Tensor) -> torch.Tensor:
         return a.zero_() if self.fault_drop else a
@@ -165,13 +170,16 @@ class LlamaAttention(nn.Module):
         T = x.shape[0]
         k_cache, v_cache = kv
         S = gemm.choose_split(self.qkv.shape[0], x.shape[1], T)
-        if ws is not None and gemm.skinny_ok(x, self.qkv) and S > 1 and ws.numel() >= S * T * self.qkv.shape[0]:
+        # (an FP8 cache has no split-K epilogue writer: its steps with prefill take linear -> rope_and_cache)
+        fp8_prefill = md.num_prefill > 0 and k_cache.dtype == attn_ops.FP8
+        if (ws is not None and gemm.skinny_ok(x, self.qkv) and S > 1 and ws.numel() >= S * T * self.qkv.shape[0]
+                and not fp8_prefill):
             p = gemm.linear_partial(x, self.qkv, ws, S, packed=self.qkv_p)
             if md.num_prefill == 0:
                 # pure decode: the attention kernel itself reduces the QKV slabs, applies RoPE
                 # and writes the new k / v into the paged cache
                 a = attn_ops.paged_decode_from_qkv(p, positions, cos_sin, k_cache, v_cache, md, self.scale,
-                                                   self.nq, self.nkv)
+                                                   self.nq, self.nkv, k_scale=self.k_scale, v_scale=self.v_scale)
                 return _proj_out(self.drop(a), self.o, ws, self.o_p, half=True)
             # split-K QKV whose epilogue kernel also applies RoPE and writes the KV cache
             q = gemm.qkv_reduce_rope_cache(p, positions, cos_sin, k_cache, v_cache, md.slot_mapping, self.nq,
@@ -179,7 +187,7 @@ class LlamaAttention(nn.Module):
         else:
             return _proj_out(self.drop(self.attend(gemm.linear(x, self.qkv, packed=self.qkv_p), positions, md,
                                                    cos_sin, kv)), self.o, ws, self.o_p)
-        a = attn_ops.paged_attention(q, k_cache, v_cache, md, self.scale)
+        a = attn_ops.paged_attention(q, k_cache, v_cache, md, self.scale, k_scale=self.k_scale, v_scale=self.v_scale)
         return _proj_out(self.drop(a), self.o, ws, self.o_p, half=True)
 
     def attend(self, qkv: torch.Tensor, positions: torch.Tensor, md: attn_ops.AttnMetadata, cos_sin: torch.Tensor,
@@ -187,9 +195,10 @@ class LlamaAttention(nn.Module):
         """RoPE + KV-cache write + paged attention from a projected [T, (nq + 2 nkv) hd] qkv."""
         k_cache, v_cache = kv
         attn_ops.rope_and_cache(qkv, positions, cos_sin, k_cache, v_cache, md.slot_mapping, self.nq, self.nkv,
-                                self.hd)
+                                self.hd, k_scale=self.k_scale, v_scale=self.v_scale)
         q = qkv.view(qkv.shape[0], self.nq + 2 * self.nkv, self.hd)[:, :self.nq]
-        return attn_ops.paged_attention(q, k_cache, v_cache, md, self.scale)
+        return attn_ops.paged_attention(q, k_cache, v_cache, md, self.scale, k_scale=self.k_scale,
+                                        v_scale=self.v_scale)
 
 
 class LlamaMLP(nn.Module):
@@ -314,6 +323,7 @@ class LlamaForCausalLM(nn.Module):
             layer.attn.o = _p(shard_cols(get(p + "self_attn.o_proj.weight"), r, tp).contiguous())
             layer.ln1 = _p(get(p + "input_layernorm.weight"))
             layer.ln2 = _p(get(p + "post_attention_layernorm.weight"))
+            layer.attn.k_scale, layer.attn.v_scale = weights.kv_scales(idx, p + "self_attn.")
             self._load_mlp_hf(i, layer.mlp, get, p)
         return self
 
@@ -338,6 +348,9 @@ class LlamaForCausalLM(nn.Module):
             out.update({p + "self_attn.q_proj.weight": q, p + "self_attn.k_proj.weight": k,
                         p + "self_attn.v_proj.weight": v, p + "self_attn.o_proj.weight": layer.attn.o,
                         p + "input_layernorm.weight": layer.ln1, p + "post_attention_layernorm.weight": layer.ln2})
+            for n in ("k_scale", "v_scale"):  # FP8 KV-cache scales: scalar fp32, written when not 1
+                if getattr(layer.attn, n) != 1.0:
+                    out[p + "self_attn." + n] = torch.tensor(getattr(layer.attn, n), dtype=torch.float32)
             out.update(self._mlp_hf_state(p, layer.mlp))
         return {k: v.detach().contiguous().cpu() for k, v in out.items()}
 
@@ -385,7 +398,9 @@ class LlamaForCausalLM(nn.Module):
         ws = self.workspace(x.shape[0])
         # the folded chain serves decode batches up to DECODE_MAX_M rows; steps carrying prefill
         # chunks above 64 rows keep the library GEMMs (hipBLASLt) of the general path
-        if ws is not None and (md.num_prefill == 0 or x.shape[0] <= gemm.SKINNY_MAX_M) and self._rowscale_ok(x):
+        fp8 = bool(kv_caches) and kv_caches[0][0].dtype == attn_ops.FP8
+        if (ws is not None and (md.num_prefill == 0 or (x.shape[0] <= gemm.SKINNY_MAX_M and not fp8))
+                and self._rowscale_ok(x)):
             return self._forward_rowscale(x, positions, md, kv_caches, ws)
         residual = None
         for i, layer in enumerate(self.layers):
@@ -496,9 +511,16 @@ class LlamaForCausalLM(nn.Module):
         x, _ = gemm.partial_add_rms_norm(pending, residual, self.norm, self.cfg.rms_eps)
         return x
 
-    def _qkv_attn_fused_ok(self, at, T: int, nparts: int, md) -> bool:
+    _carry_warned = False
+
+    def _qkv_attn_fused_ok(self, at, T: int, nparts: int, md, kc: Optional[torch.Tensor] = None) -> bool:
         # (a TP rank sharing its GPU keeps the two launches: a hand-off lost to a co-tenant has a
         # fallback only at TP = 1 -- a TP group cannot re-run one rank's step, llm_engine.py)
+        # kc: the K cache the step writes.  The launch is bf16-only, like the split-K QKV epilogue
+        # writer and the carried TP collective: an FP8 (e4m3) cache bypasses all three, decided
+        # from the dtype of the cache at hand and nothing else.
+        if kc is not None and kc.dtype == attn_ops.FP8:
+            return False
         return (md.num_prefill == 0 and gemm.QKV_ATTN_FUSED and at.nkv >= gemm.QKV_ATTN_MIN_KV
                 and gemm.fused_rows_ok(T, nparts) and md.num_decode == T
                 and not (self.st.shared_device and self.st.tp_size > 1))
@@ -510,7 +532,7 @@ class LlamaForCausalLM(nn.Module):
         kc, vc = kv
         T = residual.shape[0]
         rs = gemm.RowScale(parts, layer.eps)
-        if self._qkv_attn_fused_ok(at, T, parts.shape[0], md):
+        if self._qkv_attn_fused_ok(at, T, parts.shape[0], md, kc):
             # QKV slabs handed to the decode attention in-launch (one launch, csrc/kernels/decode_fused.hip);
             # deadlock-free on a shared GPU too: the QKV tiles never wait and dispatch first
             return gemm.qkv_attn_fused(residual, at.qkv_pf, rs, ws, positions, self.cos_sin, kc, vc, md, at.scale,
@@ -521,7 +543,9 @@ class LlamaForCausalLM(nn.Module):
         p = gemm.linear_partial_rowscale(residual, at.qkv, ws, rs, packed=at.qkv_pf,
                                          half=gemm.QKV_HALF and T <= gemm.SKINNY_MAX_M)
         if md.num_prefill == 0:
-            return attn_ops.paged_decode_from_qkv(p, positions, self.cos_sin, kc, vc, md, at.scale, at.nq, at.nkv)
+            return attn_ops.paged_decode_from_qkv(p, positions, self.cos_sin, kc, vc, md, at.scale, at.nq, at.nkv,
+                                                  k_scale=at.k_scale, v_scale=at.v_scale)
+        assert kc.dtype != attn_ops.FP8, "FP8 KV cache: steps with prefill take the general path (forward)"
         q = gemm.qkv_reduce_rope_cache(p, positions, self.cos_sin, kc, vc, md.slot_mapping, at.nq, at.nkv)
         return attn_ops.paged_attention(q, kc, vc, md, at.scale)
 
@@ -572,7 +596,7 @@ class LlamaForCausalLM(nn.Module):
         attention; gate_up split over K: gate_up | SiLU reduce | down), profiles/r5_decode_attention.md
         -- 6 there too when the collectives ride in their consumers' launches (_forward_tp_carried)."""
         car = self.st.custom_ar
-        if self._carry_ok(residual, md):
+        if self._carry_ok(residual, md, kv_caches[0][0]):
             return self._forward_tp_carried(residual, parts, positions, md, kv_caches, ws, buf, buf2)
         for i, layer in enumerate(self.layers):
             at, mlp = layer.attn, layer.mlp
@@ -599,7 +623,7 @@ class LlamaForCausalLM(nn.Module):
     carry_collectives: Optional[bool] = None
     carry_qkv: Optional[bool] = None
 
-    def _carry_ok(self, residual: torch.Tensor, md) -> bool:
+    def _carry_ok(self, residual: torch.Tensor, md, kc: Optional[torch.Tensor] = None) -> bool:
         """The carried chain (:meth:`_forward_tp_carried`) takes pure-decode steps of one 64-row tile
         on the two-shot collective (TP = 4 / 8), for shards whose gate_up is split over K (no fused
         MLP launch) and whose QKV is not fused with the attention (70B TP=8: one kv head per rank).
@@ -608,6 +632,12 @@ class LlamaForCausalLM(nn.Module):
         on = self.carry_collectives
         if on is None:
             on = os.environ.get("POLYKEY_TP_CARRY", "0") in ("1", "gate_up") and not self.st.shared_device
+        if on and kc is not None and kc.dtype == attn_ops.FP8:
+            if not LlamaForCausalLM._carry_warned:
+                LlamaForCausalLM._carry_warned = True
+                logging.getLogger(__name__).warning(
+                    "POLYKEY_TP_CARRY is ignored with an FP8 KV cache: the carried collective is bf16-only")
+            return False
         car = self.st.custom_ar
         M, H = residual.shape
         l0 = self.layers[0]

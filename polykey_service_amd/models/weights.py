@@ -113,3 +113,15 @@ class SafetensorsIndex:
         if f not in self._open:
             self._open[f] = self._safe_open(f, framework="pt")
         return self._open[f].get_tensor(name)
+
+
+def kv_scales(idx: SafetensorsIndex, prefix: str) -> Tuple[float, float]:
+    """A layer's FP8 KV-cache scales ``<prefix>k_scale`` / ``<prefix>v_scale`` (scalar tensors; 1.0
+    where the checkpoint has none).  Every TP rank reads the same value."""
+    out = []
+    for n in ("k_scale", "v_scale"):
+        s = float(idx.get(prefix + n).float().reshape(-1)[0]) if idx.has(prefix + n) else 1.0
+        if not (0.0 < s < float("inf")):
+            raise ValueError(f"{prefix}{n} = {s}: a KV-cache scale is a positive finite number")
+        out.append(s)
+    return out[0], out[1]

@@ -81,36 +81,78 @@ def decode_workspace(n_seqs: int, n_q: int, max_blocks: int, block_size: int, de
     return o, ml
 
 
+FP8 = reference.FP8  # the reduced-precision KV-cache element (OCP e4m3, csrc/kernels/kv_fp8.h)
+
+
+def cache_is_fp8(k_cache: torch.Tensor, v_cache: torch.Tensor) -> bool:
+    """Which kernel family a layer's caches take: bf16 or FP8 (e4m3).  K and V of one layer share
+    the dtype; anything else is an error, never a silent conversion."""
+    if k_cache.dtype != v_cache.dtype:
+        raise TypeError(f"K and V cache dtypes differ: {k_cache.dtype} vs {v_cache.dtype}")
+    if k_cache.dtype == FP8:
+        return True
+    if k_cache.dtype != torch.bfloat16:
+        raise TypeError(f"unsupported KV-cache dtype {k_cache.dtype}: bfloat16 or float8_e4m3fn")
+    return False
+
+
 def rope_and_cache(qkv: torch.Tensor, positions: torch.Tensor, cos_sin: torch.Tensor, k_cache: torch.Tensor,
-                   v_cache: torch.Tensor, slot_mapping: torch.Tensor, nq: int, nkv: int, hd: int = 128) -> None:
-    """In place on ``qkv`` [T, (nq+2nkv)*hd]; writes K/V of every token with slot >= 0."""
+                   v_cache: torch.Tensor, slot_mapping: torch.Tensor, nq: int, nkv: int, hd: int = 128, *,
+                   k_scale: float = 1.0, v_scale: float = 1.0) -> None:
+    """In place on ``qkv`` [T, (nq+2nkv)*hd]; writes K/V of every token with slot >= 0.  An FP8
+    cache stores ``e4m3(clamp(x / scale, -448, 448))`` (the scales are ignored for bf16)."""
     if not qkv.is_cuda:
-        reference.rope_and_cache(qkv, positions, cos_sin, k_cache, v_cache, slot_mapping, nq, nkv, hd)
+        reference.rope_and_cache(qkv, positions, cos_sin, k_cache, v_cache, slot_mapping, nq, nkv, hd,
+                                 k_scale=k_scale, v_scale=v_scale)
         return
     T = qkv.shape[0]
     assert qkv.stride(-1) == 1 and positions.dtype == torch.int32 and slot_mapping.dtype == torch.int32
-    assert cos_sin.dtype == torch.float32 and k_cache.dtype == torch.bfloat16
+    assert cos_sin.dtype == torch.float32
+    if cache_is_fp8(k_cache, v_cache):
+        native.call("pk_rope_and_cache_fp8", qkv.data_ptr(), positions.data_ptr(), cos_sin.data_ptr(),
+                    k_cache.data_ptr(), v_cache.data_ptr(), slot_mapping.data_ptr(), T, nq, nkv, hd, k_cache.shape[2],
+                    qkv.stride(0), float(k_scale), float(v_scale), native.stream_ptr())
+        return
     native.call("pk_rope_and_cache", qkv.data_ptr(), positions.data_ptr(), cos_sin.data_ptr(), k_cache.data_ptr(),
                 v_cache.data_ptr(), slot_mapping.data_ptr(), T, nq, nkv, hd, k_cache.shape[2], qkv.stride(0), 0,
                 native.stream_ptr())
 
 
 def paged_attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, md: AttnMetadata,
-                    scale: float, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                    scale: float, out: Optional[torch.Tensor] = None, *, k_scale: float = 1.0,
+                    v_scale: float = 1.0) -> torch.Tensor:
     """q: [T, nq, 128] view (row stride may exceed nq*128, e.g. inside the QKV buffer).
-    Returns out: [T, nq*128] bf16."""
+    Returns out: [T, nq*128] bf16.  An FP8 cache is read as ``scale * byte`` (k_scale folded into
+    the softmax scale, v_scale into the normalisation; both ignored for bf16)."""
     T, nq, hd = q.shape
     nkv = k_cache.shape[1]
     bs = k_cache.shape[2]
     if out is None:
         out = torch.empty((T, nq * hd), dtype=q.dtype, device=q.device)
     if not q.is_cuda:
-        _reference(q, k_cache, v_cache, md, scale, out)
+        _reference(q, k_cache, v_cache, md, scale, out, k_scale, v_scale)
         return out
     assert hd == 128 and q.stride(-1) == 1 and q.stride(1) == hd
     apply_decode_fill()
     stream = native.stream_ptr()
     nd = md.num_decode
+    if cache_is_fp8(k_cache, v_cache):
+        if nd > 0:
+            bt = md.decode_block_tables
+            native.call("pk_paged_decode_fp8", out.data_ptr(), q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(),
+                        bt.data_ptr(), md.decode_context_lens.data_ptr(),
+                        native.ptr(md.decode_part_o) or 0, native.ptr(md.decode_part_ml) or 0,
+                        nd, nq, nkv, bs, bt.stride(0), q.stride(0), out.stride(0),
+                        float(scale), int(md.decode_max_ctx), float(k_scale), float(v_scale), stream)
+        if md.num_prefill > 0:
+            bt = md.prefill_block_tables
+            qp = q[nd:]
+            op = out[nd:]
+            native.call("pk_paged_prefill_fp8", op.data_ptr(), qp.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(),
+                        bt.data_ptr(), md.prefill_context_lens.data_ptr(), md.prefill_cu_q.data_ptr(),
+                        md.num_prefill, nq, nkv, bs, bt.shape[1], q.stride(0), out.stride(0),
+                        int(md.max_prefill_q_len), float(scale), float(k_scale), float(v_scale), stream)
+        return out
     if nd > 0:
         bt = md.decode_block_tables
         native.call("pk_paged_decode", out.data_ptr(), q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(),
@@ -129,16 +171,17 @@ def paged_attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tenso
     return out
 
 
-def _reference(q, k_cache, v_cache, md: AttnMetadata, scale, out):
+def _reference(q, k_cache, v_cache, md: AttnMetadata, scale, out, k_scale=1.0, v_scale=1.0):
     nd = md.num_decode
     o3 = out.view(out.shape[0], q.shape[1], q.shape[2])
     if nd > 0:
         cu = torch.arange(nd + 1, dtype=torch.int32)
         o3[:nd] = reference.paged_attention(q[:nd].contiguous(), k_cache, v_cache, md.decode_block_tables.cpu(),
-                                            md.decode_context_lens.cpu(), cu, scale)
+                                            md.decode_context_lens.cpu(), cu, scale, k_scale=k_scale, v_scale=v_scale)
     if md.num_prefill > 0:
         o3[nd:] = reference.paged_attention(q[nd:].contiguous(), k_cache, v_cache, md.prefill_block_tables.cpu(),
-                                            md.prefill_context_lens.cpu(), md.prefill_cu_q.cpu(), scale)
+                                            md.prefill_context_lens.cpu(), md.prefill_cu_q.cpu(), scale, k_scale=k_scale,
+                                            v_scale=v_scale)
 
 
 def default_scale(head_dim: int = 128) -> float:
@@ -146,7 +189,8 @@ def default_scale(head_dim: int = 128) -> float:
 
 
 def paged_decode_from_qkv(p, positions: torch.Tensor, cos_sin: torch.Tensor, k_cache: torch.Tensor,
-                          v_cache: torch.Tensor, md: AttnMetadata, scale: float, nq: int, nkv: int) -> torch.Tensor:
+                          v_cache: torch.Tensor, md: AttnMetadata, scale: float, nq: int, nkv: int, *,
+                          k_scale: float = 1.0, v_scale: float = 1.0) -> torch.Tensor:
     """Pure-decode attention straight from the fused QKV projection's split-K slabs
     (``gemm.Partial``): the attention kernel reduces the slabs, applies RoPE, writes the new
     k / v into the paged cache and attends — one kernel instead of reduce+RoPE+cache then
@@ -156,6 +200,14 @@ def paged_decode_from_qkv(p, positions: torch.Tensor, cos_sin: torch.Tensor, k_c
     T = p.M
     out = torch.empty((T, nq * 128), dtype=torch.bfloat16, device=p.buf.device)
     bt = md.decode_block_tables
+    if cache_is_fp8(k_cache, v_cache):
+        native.call("pk_paged_decode_qkv_fp8", out.data_ptr(), p.buf.data_ptr(), p.S, p.M, positions.data_ptr(),
+                    cos_sin.data_ptr(), md.slot_mapping.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(),
+                    bt.data_ptr(), md.decode_context_lens.data_ptr(), native.ptr(md.decode_part_o) or 0,
+                    native.ptr(md.decode_part_ml) or 0, md.num_decode, nq, nkv, k_cache.shape[2], bt.stride(0),
+                    out.stride(0), float(scale), int(md.decode_max_ctx), float(k_scale), float(v_scale),
+                    native.stream_ptr())
+        return out
     native.call("pk_paged_decode_qkv", out.data_ptr(), p.buf.data_ptr(), p.S, p.M, positions.data_ptr(),
                 cos_sin.data_ptr(), md.slot_mapping.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(),
                 bt.data_ptr(), md.decode_context_lens.data_ptr(), native.ptr(md.decode_part_o) or 0,

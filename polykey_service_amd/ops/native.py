@@ -40,6 +40,12 @@ SIGNATURES = {
     "pk_set_decode_fill": [I32],
     "pk_paged_decode_qkv": [P, P, I32, I32, P, P, P, P, P, P, P, P, P, I32, I32, I32, I32, I32, I32, F32, I32, P],
     "pk_paged_prefill": [P, P, P, P, P, P, P, P, I32, I32, I32, I32, I32, I32, I32, I32, F32, P],
+    # FP8 (e4m3) KV cache: the same launches over byte caches + k_scale, v_scale
+    "pk_rope_and_cache_fp8": [P, P, P, P, P, P, I32, I32, I32, I32, I32, I32, F32, F32, P],
+    "pk_paged_decode_fp8": [P, P, P, P, P, P, P, P, I32, I32, I32, I32, I32, I32, I32, F32, I32, F32, F32, P],
+    "pk_paged_decode_qkv_fp8": [P, P, I32, I32, P, P, P, P, P, P, P, P, P, I32, I32, I32, I32, I32, I32, F32, I32,
+                                F32, F32, P],
+    "pk_paged_prefill_fp8": [P, P, P, P, P, P, P, I32, I32, I32, I32, I32, I32, I32, I32, F32, F32, F32, P],
     "pk_sample": [P, P, P, P, P, P, P, P, P, I32, I32, I32, I32, P],
     "pk_sample_alt": [P, P, P, P, P, P, P, P, I32, I32, I32, I32, P, I64, P, I32, P],
     "pk_logprobs": [P, P, P, P, I32, I32, I32, I32, P],

@@ -128,10 +128,35 @@ def k_cache_logical(k_cache: torch.Tensor) -> torch.Tensor:
     return k_cache.reshape(nb, nkv, bs * hd)[:, :, kcache_index(bs, k_cache.device).view(-1)].view(nb, nkv, bs, hd)
 
 
+FP8 = torch.float8_e4m3fn
+FP8_MAX = 448.0
+
+
+def quantize_fp8(x: torch.Tensor, scale: float = 1.0) -> torch.Tensor:
+    """The FP8 KV-cache byte of ``x``: e4m3 round-to-nearest-even of clamp(x / scale, -448, 448),
+    in fp32 (+-inf and anything beyond +-448 store +-448; subnormals down to 2^-9 are kept)."""
+    return (x.float() / scale).clamp(-FP8_MAX, FP8_MAX).to(FP8)
+
+
+def dequantize_fp8(c: torch.Tensor, scale: float = 1.0) -> torch.Tensor:
+    """fp32 values an FP8 cache holds: scale * byte."""
+    return c.float() * scale
+
+
+def _store(cache_flat: torch.Tensor, index: tuple, rows: torch.Tensor, scale: float) -> None:
+    """cache_flat[index] = rows in the cache's dtype (FP8 caches: quantised, indexed as bytes)."""
+    if cache_flat.dtype == FP8:
+        cache_flat.view(torch.uint8)[index] = quantize_fp8(rows, scale).view(torch.uint8)
+    else:
+        cache_flat[index] = rows.to(cache_flat.dtype)
+
+
 def rope_and_cache(qkv: torch.Tensor, positions: torch.Tensor, cos_sin: torch.Tensor,
                    k_cache: Optional[torch.Tensor], v_cache: Optional[torch.Tensor],
-                   slot_mapping: Optional[torch.Tensor], nq: int, nkv: int, hd: int) -> torch.Tensor:
-    """Rotate q,k of the fused QKV output in place and scatter k,v into the paged cache."""
+                   slot_mapping: Optional[torch.Tensor], nq: int, nkv: int, hd: int,
+                   k_scale: float = 1.0, v_scale: float = 1.0) -> torch.Tensor:
+    """Rotate q,k of the fused QKV output in place and scatter k,v into the paged cache (an FP8
+    cache gets the quantised values of the rotated, already rounded rows)."""
     T = qkv.shape[0]
     view = qkv.view(T, nq + 2 * nkv, hd)
     q, k, v = view[:, :nq], view[:, nq:nq + nkv], view[:, nq + nkv:]
@@ -147,28 +172,32 @@ def rope_and_cache(qkv: torch.Tensor, positions: torch.Tensor, cos_sin: torch.Te
             n, nkv_ = blk.numel(), k_cache.shape[1]
             kflat = k_cache.view(k_cache.shape[0], nkv_, bs * hd)
             pos = kcache_index(bs, k_cache.device)[off]  # [n, 128] fragment-native positions
-            kflat[blk.view(n, 1, 1), torch.arange(nkv_, device=k_cache.device).view(1, nkv_, 1),
-                  pos.view(n, 1, hd)] = k[valid].to(k_cache.dtype)
+            _store(kflat, (blk.view(n, 1, 1), torch.arange(nkv_, device=k_cache.device).view(1, nkv_, 1),
+                           pos.view(n, 1, hd)), k[valid], k_scale)
             vflat = v_cache.view(v_cache.shape[0], nkv_, bs * hd)
             vpos = vcache_index(bs, v_cache.device)[off]
-            vflat[blk.view(n, 1, 1), torch.arange(nkv_, device=v_cache.device).view(1, nkv_, 1),
-                  vpos.view(n, 1, hd)] = v[valid].to(v_cache.dtype)
+            _store(vflat, (blk.view(n, 1, 1), torch.arange(nkv_, device=v_cache.device).view(1, nkv_, 1),
+                           vpos.view(n, 1, hd)), v[valid], v_scale)
     return q
 
 
 # ------------------------------------------------------------------------- attention
 def gather_kv(k_cache, v_cache, block_table, n_tokens):
-    """→ K [n, n_kv, D], V [n, n_kv, D] for one sequence."""
+    """→ K [n, n_kv, D], V [n, n_kv, D] for one sequence (FP8 caches: the raw bytes, as FP8)."""
     bs = k_cache.shape[2]
     nb = (n_tokens + bs - 1) // bs
     blocks = block_table[:nb].long()
+    if k_cache.dtype == FP8:  # index as bytes
+        k, v = gather_kv(k_cache.view(torch.uint8), v_cache.view(torch.uint8), block_table, n_tokens)
+        return k.view(FP8), v.view(FP8)
     k = k_cache_logical(k_cache[blocks]).permute(0, 2, 1, 3).reshape(nb * bs, k_cache.shape[1], -1)[:n_tokens]
     v = v_cache_logical(v_cache[blocks]).permute(0, 2, 1, 3).reshape(nb * bs, v_cache.shape[1], -1)[:n_tokens]
     return k, v
 
 
 def paged_attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, block_tables: torch.Tensor,
-                    context_lens: torch.Tensor, cu_seqlens_q: torch.Tensor, scale: float) -> torch.Tensor:
+                    context_lens: torch.Tensor, cu_seqlens_q: torch.Tensor, scale: float,
+                    k_scale: float = 1.0, v_scale: float = 1.0) -> torch.Tensor:
     """Causal GQA attention of each sequence's new query tokens against its whole paged
     context.  Query ``i`` of a chunk of ``L`` tokens sits at absolute position
     ``ctx - L + i`` and attends to keys ``[0, ctx - L + i]``.  q: [T, nq, D] → [T, nq, D]."""
@@ -184,6 +213,8 @@ def paged_attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tenso
         if L == 0 or ctx == 0:
             continue
         k, v = gather_kv(k_cache, v_cache, block_tables[s], ctx)
+        if k_cache.dtype == FP8:  # attention over scale * byte
+            k, v = dequantize_fp8(k, k_scale), dequantize_fp8(v, v_scale)
         k = k.float().repeat_interleave(g, dim=1)  # [ctx, nq, D]
         v = v.float().repeat_interleave(g, dim=1)
         qs = q[a:b].float()  # [L, nq, D]

@@ -1,7 +1,7 @@
 """Decode-step time of the graph-captured engine (Llama-3-8B random init, 64 sequences, prompt
 256), for A/B runs of kernel-library builds:
 
-    python tools/ab_decode.py [--steps 128] [--reps 3]
+    python tools/ab_decode.py [--steps 128] [--reps 3] [--kv-cache-dtype fp8]
 
 decode ms/step = (T(prompt + 1 + steps new tokens) - T(1 new token)) / steps, best of ``reps``."""
 import argparse
@@ -27,10 +27,11 @@ def main() -> None:
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--tag", default=os.environ.get("AB_TAG", ""))
     ap.add_argument("--eager", action="store_true", help="no HIP graphs (PMC runs count per dispatch)")
+    ap.add_argument("--kv-cache-dtype", default="auto", help="auto | bf16 | fp8 (the KV-cache element type)")
     a = ap.parse_args()
     max_len = max(2048, (a.prompt + a.steps + 64 + 511) // 512 * 512)
     eng = LLMEngine(EngineConfig(model=a.model, max_num_seqs=a.batch, device="cuda:0", max_model_len=max_len,
-                                 hip_graphs=not a.eager))
+                                 hip_graphs=not a.eager, kv_cache_dtype=a.kv_cache_dtype))
     g = torch.Generator().manual_seed(0)
     hi = min(30000, eng.mcfg.vocab_size - 1)
     prompts = [torch.randint(10, hi, (a.prompt,), generator=g).tolist() for _ in range(a.batch)]
@@ -47,7 +48,9 @@ def main() -> None:
         full, one = run(a.steps + 1), run(1)
         per_step.append((full - one) / a.steps * 1e3)
     print(json.dumps({"tag": a.tag, "decode_ms_per_step": round(min(per_step), 4),
-                      "all": [round(x, 4) for x in per_step], "batch": a.batch, "prompt": a.prompt}), flush=True)
+                      "all": [round(x, 4) for x in per_step], "batch": a.batch, "prompt": a.prompt,
+                      "kv_cache_dtype": eng.cfg.kv_cache_dtype, "kv_blocks": eng.runner.num_blocks,
+                      "kv_bytes_per_block": eng.runner.kv_bytes_per_block()}), flush=True)
     eng.shutdown()
 
 
