@@ -1,5 +1,5 @@
 // Paged attention (decode + varlen causal prefill) for gfx950, head_dim = 128, bf16 KV -- or FP8
-// (e4m3) KV widened to bf16 on the way to the same MFMAs (kv_fp8.h; the *_fp8 entry points).
+// (e4m3) KV widened to bf16 on the way to the same MFMAs (kv_fp8.h; the kv_dtype argument of every entry point).
 //
 // One wave computes 16 "columns" against a stream of 32-key steps with
 // mfma_f32_16x16x32_bf16.  A column is (query row, head): in DECODE the 16 columns are
@@ -32,29 +32,18 @@ using namespace pk;
 
 namespace {
 
-template <int kPart, int NW, bool FROM_QKV, int SS = 0>
+// CT: the cache element.  SC is a pack, empty for bf16 and one KvScale for an FP8 (e4m3) cache
+// (scale2 then carries the K scale, kv_fp8.h), so the bf16 kernels take no scale argument.
+template <int kPart, int NW, bool FROM_QKV, int SS, typename CT, typename... SC>
 __global__ void __launch_bounds__(64 * NW) paged_decode_kernel(
-    bf16_t* __restrict__ out, const bf16_t* __restrict__ q, bf16_t* __restrict__ kc,
-    bf16_t* __restrict__ vc, const int* __restrict__ block_tables, const int* __restrict__ context_lens,
+    bf16_t* __restrict__ out, const bf16_t* __restrict__ q, CT* __restrict__ kc,
+    CT* __restrict__ vc, const int* __restrict__ block_tables, const int* __restrict__ context_lens,
     float* __restrict__ part_o, float* __restrict__ part_ml, int n_q, int n_kv, int bs,
-    int max_blocks, int q_stride, int out_stride, int n_parts, float scale2, const QkvIn qi) {
+    int max_blocks, int q_stride, int out_stride, int n_parts, float scale2, const QkvIn qi, const SC... sc) {
   __shared__ DecodeLds<kPart, NW> lds;
-  decode_tile<kPart, NW, FROM_QKV, SS>(out, q, kc, vc, block_tables, context_lens, part_o, part_ml, n_q, n_kv,
-                                       bs, max_blocks, q_stride, out_stride, n_parts, scale2, qi, blockIdx.x, blockIdx.y,
-                                       blockIdx.z, gridDim.z, lds, Flow{});
-}
-
-// the same workgroup body over an FP8 (e4m3) cache: scale2 carries the K scale (kv_fp8.h)
-template <int kPart, int NW, bool FROM_QKV, int SS = 0>
-__global__ void __launch_bounds__(64 * NW) paged_decode_fp8_kernel(
-    bf16_t* __restrict__ out, const bf16_t* __restrict__ q, fp8_t* __restrict__ kc,
-    fp8_t* __restrict__ vc, const int* __restrict__ block_tables, const int* __restrict__ context_lens,
-    float* __restrict__ part_o, float* __restrict__ part_ml, int n_q, int n_kv, int bs,
-    int max_blocks, int q_stride, int out_stride, int n_parts, float scale2, const QkvIn qi, const KvScale ks) {
-  __shared__ DecodeLds<kPart, NW> lds;
-  decode_tile<kPart, NW, FROM_QKV, SS, 0, 0, fp8_t>(out, q, kc, vc, block_tables, context_lens, part_o, part_ml, n_q,
-                                                    n_kv, bs, max_blocks, q_stride, out_stride, n_parts, scale2, qi,
-                                                    blockIdx.x, blockIdx.y, blockIdx.z, gridDim.z, lds, Flow{}, ks);
+  decode_tile<kPart, NW, FROM_QKV, SS, 0, 0, CT>(out, q, kc, vc, block_tables, context_lens, part_o, part_ml, n_q,
+                                                 n_kv, bs, max_blocks, q_stride, out_stride, n_parts, scale2, qi,
+                                                 blockIdx.x, blockIdx.y, blockIdx.z, gridDim.z, lds, Flow{}, sc...);
 }
 
 // ----------------------------------------------------------------------------- prefill
@@ -336,22 +325,49 @@ __global__ void __launch_bounds__(64 * NW, 2) paged_prefill_mfma32_kernel(
 }
 
 
-constexpr int kDecodePart = 512;  // keys per decode partition (ops/attention.py _PART must match)
-
 }  // namespace
+
+// Fewer workgroups than this at the full partition -> 128-key partitions (pk_set_decode_fill).  64:
+// the 70B TP=8 rank's 64 sequences x 1 kv head stay at 512 keys (one workgroup per sequence, no
+// merge launch): per-rank step 6.52 vs 6.54 ms at 256 (128-key partitions + merge),
+// profiles/r5_attn_ab4.jsonl
+static int g_decode_fill = 64;
+static int g_decode_z = 4;  // max partition workgroups per (seq, kv head) (pk_set_decode_z)
 
 // Workspace for decode: part_o [n_seqs, n_q, n_parts, 128] fp32, part_ml [n_seqs, n_q, n_parts, 2] fp32,
 // n_parts counted in the smallest partition (kDecodePartSmall, ops/attention.py _PART_MIN).
-PK_EXPORT int pk_decode_num_parts(int max_context) { return (max_context + kDecodePartSmall - 1) / kDecodePartSmall; }
-
+//
 // Keys per partition of a launch: 512, or 128 when (seq, kv head) pairs x partitions would leave
 // most CUs idle -- the 70B TP=8 shard has ONE kv head per rank, so 64 sequences are 64 workgroups
 // at 512 keys (22.5 us for 12.6 MB of K/V, profiles/r4_solo_70b_tp8_unfused_kstats.md) and 256 at
 // 128 (4 partials per sequence, merged after).
-int decode_part(int n_seqs, int n_kv, int max_ctx) {
+int decode_plan(DecodePlan& plan, int n_seqs, int n_q, int n_kv, int bs, int max_blocks, int max_ctx,
+                const void* part_o, const void* part_ml) {
+  if (n_q % n_kv || n_q / n_kv > 16 || bs % 32 || bs <= 0) return -1;  // K tiles: 32 keys
+  // max_ctx bounds the contexts of this launch (<= 0: the block-table capacity).  A launch
+  // known to stay within one partition needs no partition grid and no merge kernel.
+  if (max_ctx <= 0 || max_ctx > max_blocks * bs) max_ctx = max_blocks * bs;
   const int big = (max_ctx + kDecodePart - 1) / kDecodePart;
-  const int z = big < g_decode_z ? big : g_decode_z;
-  return n_seqs * n_kv * z < g_decode_fill ? kDecodePartSmall : kDecodePart;
+  plan.part = n_seqs * n_kv * (big < g_decode_z ? big : g_decode_z) < g_decode_fill ? kDecodePartSmall : kDecodePart;
+  plan.n_parts = (max_ctx + plan.part - 1) / plan.part;
+  if (plan.n_parts > 1 && (part_o == nullptr || part_ml == nullptr)) return -2;
+  // z is capped: a short context leaves the extra z-workgroups idle, and graph capture fixes
+  // the grid for max_model_len, so a z of n_parts would launch mostly-empty workgroups
+  plan.z = plan.n_parts < g_decode_z ? plan.n_parts : g_decode_z;
+  return 0;
+}
+
+// Sequences with more than one partition are merged by a second kernel (an in-launch merge by
+// the last partition measured slower, profiles/r5_tp_ab.jsonl, and was removed in round 6).
+int decode_merge(const DecodePlan& plan, void* out, const void* part_o, const void* part_ml,
+                 const void* context_lens, int n_seqs, int n_q, int out_stride, hipStream_t stream) {
+  if (plan.n_parts == 1) return 0;
+  const auto merge = plan.part == kDecodePartSmall ? &paged_decode_reduce_kernel<kDecodePartSmall>
+                                                   : &paged_decode_reduce_kernel<kDecodePart>;
+  merge<<<dim3(n_q, n_seqs), 128, 0, stream>>>(
+      static_cast<bf16_t*>(out), static_cast<const float*>(part_o), static_cast<const float*>(part_ml),
+      static_cast<const int*>(context_lens), n_q, out_stride, plan.n_parts, plan.z);
+  return PK_CHECK_LAUNCH();
 }
 
 // Workgroup count below which decode takes 128-key partitions (default 64; 0: always 512 keys).
@@ -363,89 +379,74 @@ PK_EXPORT int pk_set_decode_fill(int n) {
   return 0;
 }
 
-// ks: null for a bf16 cache, the two scales of an FP8 (e4m3) cache
-template <int P>
-static int decode_launch_p(void* out, const void* q, const QkvIn& qi, const void* k_cache, const void* v_cache,
-                           const void* block_tables, const void* context_lens, void* part_o, void* part_ml,
-                           int n_seqs, int n_q, int n_kv, int bs, int max_blocks, int q_stride,
-                           int out_stride, float scale, int max_ctx, hipStream_t stream, const KvScale* ks) {
-  const int n_parts = (max_ctx + P - 1) / P;
-  if (n_parts > 1 && (part_o == nullptr || part_ml == nullptr)) return -2;
-  // z is capped: a short context leaves the extra z-workgroups idle, and graph capture fixes
-  // the grid for max_model_len, so a z of n_parts would launch mostly-empty workgroups
-  dim3 grid(n_kv, n_seqs, n_parts < g_decode_z ? n_parts : g_decode_z);
-#define PK_DECODE_ARGS_T(T, SC)                                                                                   \
-  static_cast<bf16_t*>(out), static_cast<const bf16_t*>(q), static_cast<T*>(const_cast<void*>(k_cache)),         \
-      static_cast<T*>(const_cast<void*>(v_cache)), static_cast<const int*>(block_tables),                        \
-      static_cast<const int*>(context_lens), static_cast<float*>(part_o), static_cast<float*>(part_ml),          \
-      n_q, n_kv, bs, max_blocks, q_stride, out_stride, n_parts, (SC) * kLog2e, qi
-#define PK_DECODE_ARGS PK_DECODE_ARGS_T(bf16_t, scale)
-#define PK_DECODE_ARGS8 PK_DECODE_ARGS_T(fp8_t, scale * ks->k), *ks
-  if (ks != nullptr) {
-    if (qi.partial != nullptr) {
-      switch (qi.S) {
-        case 2: paged_decode_fp8_kernel<P, kDecodeWaves, true, 2><<<grid, 64 * kDecodeWaves, 0, stream>>>(PK_DECODE_ARGS8); break;
-        case 4: paged_decode_fp8_kernel<P, kDecodeWaves, true, 4><<<grid, 64 * kDecodeWaves, 0, stream>>>(PK_DECODE_ARGS8); break;
-        case 8: paged_decode_fp8_kernel<P, kDecodeWaves, true, 8><<<grid, 64 * kDecodeWaves, 0, stream>>>(PK_DECODE_ARGS8); break;
-        case 16: paged_decode_fp8_kernel<P, kDecodeWaves, true, 16><<<grid, 64 * kDecodeWaves, 0, stream>>>(PK_DECODE_ARGS8); break;
-        default: paged_decode_fp8_kernel<P, kDecodeWaves, true, 0><<<grid, 64 * kDecodeWaves, 0, stream>>>(PK_DECODE_ARGS8); break;
-      }
-    } else
-      paged_decode_fp8_kernel<P, kDecodeWaves, false><<<grid, 64 * kDecodeWaves, 0, stream>>>(PK_DECODE_ARGS8);
-  } else
-  // (the K/V prefetch across the slab reduction for launches that leave most CUs idle, PRE,
-  // measured slower: profiles/r5_attn_ab4.jsonl)
-  if (qi.partial != nullptr) {
-    switch (qi.S) {
-      case 2: paged_decode_kernel<P, kDecodeWaves, true, 2><<<grid, 64 * kDecodeWaves, 0, stream>>>(PK_DECODE_ARGS); break;
-      case 4: paged_decode_kernel<P, kDecodeWaves, true, 4><<<grid, 64 * kDecodeWaves, 0, stream>>>(PK_DECODE_ARGS); break;
-      case 8: paged_decode_kernel<P, kDecodeWaves, true, 8><<<grid, 64 * kDecodeWaves, 0, stream>>>(PK_DECODE_ARGS); break;
-      case 16: paged_decode_kernel<P, kDecodeWaves, true, 16><<<grid, 64 * kDecodeWaves, 0, stream>>>(PK_DECODE_ARGS); break;
-      default: paged_decode_kernel<P, kDecodeWaves, true, 0><<<grid, 64 * kDecodeWaves, 0, stream>>>(PK_DECODE_ARGS); break;
-    }
-  } else
-    paged_decode_kernel<P, kDecodeWaves, false><<<grid, 64 * kDecodeWaves, 0, stream>>>(PK_DECODE_ARGS);
-#undef PK_DECODE_ARGS8
-#undef PK_DECODE_ARGS
-#undef PK_DECODE_ARGS_T
-  int rc = PK_CHECK_LAUNCH();
-  if (rc || n_parts == 1) return rc;
-  dim3 g2(n_q, n_seqs);
-  paged_decode_reduce_kernel<P><<<g2, 128, 0, stream>>>(
-      static_cast<bf16_t*>(out), static_cast<const float*>(part_o), static_cast<const float*>(part_ml),
-      static_cast<const int*>(context_lens), n_q, out_stride, n_parts, static_cast<int>(grid.z));
-  return PK_CHECK_LAUNCH();
+PK_EXPORT int pk_set_decode_z(int z) {
+  if (z < 1) return -1;
+  g_decode_z = z;
+  return 0;
 }
 
-// Sequences with more than one partition are merged by a second kernel (an in-launch merge by
-// the last partition measured slower, profiles/r5_tp_ab.jsonl, and was removed in round 6).
-static int decode_launch(void* out, const void* q, const QkvIn& qi, const void* k_cache, const void* v_cache,
+// One decode launch at P keys per partition: the kernel for (slabs or q, compile-time split count).
+// (the K/V prefetch across the slab reduction for launches that leave most CUs idle, PRE,
+// measured slower: profiles/r5_attn_ab4.jsonl)
+template <int P, typename CT, typename... SC>
+static int decode_launch_p(const DecodePlan& plan, void* out, const void* q, const QkvIn& qi, void* k_cache,
+                           void* v_cache, const void* block_tables, const void* context_lens, void* part_o,
+                           void* part_ml, int n_seqs, int n_q, int n_kv, int bs, int max_blocks, int q_stride,
+                           int out_stride, float scale, hipStream_t stream, SC... sc) {
+  auto go = [&](auto from_qkv, auto ss) {
+    paged_decode_kernel<P, kDecodeWaves, decltype(from_qkv)::value, decltype(ss)::value, CT, SC...>
+        <<<dim3(n_kv, n_seqs, plan.z), 64 * kDecodeWaves, 0, stream>>>(
+            static_cast<bf16_t*>(out), static_cast<const bf16_t*>(q), static_cast<CT*>(k_cache),
+            static_cast<CT*>(v_cache), static_cast<const int*>(block_tables), static_cast<const int*>(context_lens),
+            static_cast<float*>(part_o), static_cast<float*>(part_ml), n_q, n_kv, bs, max_blocks, q_stride,
+            out_stride, plan.n_parts, scale * kLog2e, qi, sc...);
+  };
+  using std::integral_constant;
+  if (qi.partial == nullptr) {
+    go(std::false_type{}, integral_constant<int, 0>{});
+  } else {
+    switch (qi.S) {
+      case 2: go(std::true_type{}, integral_constant<int, 2>{}); break;
+      case 4: go(std::true_type{}, integral_constant<int, 4>{}); break;
+      case 8: go(std::true_type{}, integral_constant<int, 8>{}); break;
+      case 16: go(std::true_type{}, integral_constant<int, 16>{}); break;
+      default: go(std::true_type{}, integral_constant<int, 0>{}); break;
+    }
+  }
+  const int rc = PK_CHECK_LAUNCH();
+  return rc ? rc : decode_merge(plan, out, part_o, part_ml, context_lens, n_seqs, n_q, out_stride, stream);
+}
+
+// qi.partial null: q given; else the QKV slabs.  kv_dtype, k_scale, v_scale: kv_fp8.h with_kv_type
+// (an FP8 cache's pointers address bytes at the element offsets of the bf16 layout).
+static int decode_launch(void* out, const void* q, const QkvIn& qi, void* k_cache, void* v_cache,
                          const void* block_tables, const void* context_lens, void* part_o, void* part_ml,
-                         int n_seqs, int n_q, int n_kv, int bs, int max_blocks, int q_stride,
-                         int out_stride, float scale, int max_ctx, hipStream_t stream,
-                         const KvScale* ks = nullptr) {
-  if (n_seqs <= 0) return 0;
-  if (n_q % n_kv || n_q / n_kv > 16 || bs % 32 || bs <= 0) return -1;  // K tiles: 32 keys
-  // max_ctx bounds the contexts of this launch (<= 0: the block-table capacity).  A launch
-  // known to stay within one partition needs no partition grid and no merge kernel.
-  if (max_ctx <= 0 || max_ctx > max_blocks * bs) max_ctx = max_blocks * bs;
-  if (decode_part(n_seqs, n_kv, max_ctx) == kDecodePartSmall)
-    return decode_launch_p<kDecodePartSmall>(out, q, qi, k_cache, v_cache, block_tables, context_lens, part_o, part_ml,
-                                             n_seqs, n_q, n_kv, bs, max_blocks, q_stride, out_stride, scale,
-                                             max_ctx, stream, ks);
-  return decode_launch_p<kDecodePart>(out, q, qi, k_cache, v_cache, block_tables, context_lens, part_o, part_ml,
-                                      n_seqs, n_q, n_kv, bs, max_blocks, q_stride, out_stride, scale, max_ctx,
-                                      stream, ks);
+                         int n_seqs, int n_q, int n_kv, int bs, int max_blocks, int q_stride, int out_stride,
+                         float scale, int max_ctx, int kv_dtype, float k_scale, float v_scale, hipStream_t stream) {
+  return with_kv_type(kv_dtype, k_scale, v_scale, [&](auto ct, auto... sc) {
+    using CT = decltype(ct);
+    if (n_seqs <= 0) return 0;
+    DecodePlan plan;
+    if (const int rc = decode_plan(plan, n_seqs, n_q, n_kv, bs, max_blocks, max_ctx, part_o, part_ml)) return rc;
+    auto launch = [&](auto part) {  // an FP8 cache: the K scale rides on the softmax scale
+      return decode_launch_p<decltype(part)::value, CT>(plan, out, q, qi, k_cache, v_cache, block_tables, context_lens,
+                                                        part_o, part_ml, n_seqs, n_q, n_kv, bs, max_blocks, q_stride,
+                                                        out_stride, (scale * ... * sc.k), stream, sc...);
+    };
+    return plan.part == kDecodePartSmall ? launch(std::integral_constant<int, kDecodePartSmall>{})
+                                         : launch(std::integral_constant<int, kDecodePart>{});
+  });
 }
 
 // max_blocks: block-table row stride; max_ctx: bound on every context of this launch (<= 0: no bound)
 PK_EXPORT int pk_paged_decode(void* out, const void* q, const void* k_cache, const void* v_cache,
                               const void* block_tables, const void* context_lens, void* part_o, void* part_ml,
                               int n_seqs, int n_q, int n_kv, int bs, int max_blocks, int q_stride,
-                              int out_stride, float scale, int max_ctx, hipStream_t stream) {
-  const QkvIn none{};
-  return decode_launch(out, q, none, k_cache, v_cache, block_tables, context_lens, part_o, part_ml, n_seqs,
-                       n_q, n_kv, bs, max_blocks, q_stride, out_stride, scale, max_ctx, stream);
+                              int out_stride, float scale, int max_ctx, int kv_dtype, float k_scale, float v_scale,
+                              hipStream_t stream) {
+  return decode_launch(out, q, QkvIn{}, const_cast<void*>(k_cache), const_cast<void*>(v_cache), block_tables,
+                       context_lens, part_o, part_ml, n_seqs, n_q, n_kv, bs, max_blocks, q_stride, out_stride, scale,
+                       max_ctx, kv_dtype, k_scale, v_scale, stream);
 }
 
 // Decode attention straight from the fused QKV projection's split-K slabs [S, M, (n_q+2n_kv)*128]
@@ -454,48 +455,12 @@ PK_EXPORT int pk_paged_decode_qkv(void* out, const void* partial, int S, int M, 
                                   const void* cos_sin, const void* slots, void* k_cache, void* v_cache,
                                   const void* block_tables, const void* context_lens, void* part_o, void* part_ml,
                                   int n_seqs, int n_q, int n_kv, int bs, int max_blocks, int out_stride, float scale,
-                                  int max_ctx, hipStream_t stream) {
+                                  int max_ctx, int kv_dtype, float k_scale, float v_scale, hipStream_t stream) {
   if (partial == nullptr || S < 1 || M < n_seqs) return -1;
-  QkvIn qi{static_cast<const float*>(partial), static_cast<const int*>(positions), static_cast<const float*>(cos_sin),
-           static_cast<const int*>(slots), S, M};
-  return decode_launch(out, nullptr, qi, k_cache, v_cache, block_tables, context_lens, part_o, part_ml,
-                       n_seqs, n_q, n_kv, bs, max_blocks, 0, out_stride, scale, max_ctx, stream);
-}
-
-// The two decode entry points over an FP8 (e4m3) cache: the cache pointers address bytes, element
-// offsets are those of the bf16 layout, k_scale / v_scale are the layer's scales (kv_fp8.h).
-PK_EXPORT int pk_paged_decode_fp8(void* out, const void* q, const void* k_cache, const void* v_cache,
-                                  const void* block_tables, const void* context_lens, void* part_o, void* part_ml,
-                                  int n_seqs, int n_q, int n_kv, int bs, int max_blocks, int q_stride,
-                                  int out_stride, float scale, int max_ctx, float k_scale, float v_scale,
-                                  hipStream_t stream) {
-  if (!kv_scales_ok(k_scale, v_scale)) return -1;
-  const QkvIn none{};
-  const KvScale ks{k_scale, v_scale};
-  return decode_launch(out, q, none, k_cache, v_cache, block_tables, context_lens, part_o, part_ml, n_seqs,
-                       n_q, n_kv, bs, max_blocks, q_stride, out_stride, scale, max_ctx, stream, &ks);
-}
-
-PK_EXPORT int pk_paged_decode_qkv_fp8(void* out, const void* partial, int S, int M, const void* positions,
-                                      const void* cos_sin, const void* slots, void* k_cache, void* v_cache,
-                                      const void* block_tables, const void* context_lens, void* part_o,
-                                      void* part_ml, int n_seqs, int n_q, int n_kv, int bs, int max_blocks,
-                                      int out_stride, float scale, int max_ctx, float k_scale, float v_scale,
-                                      hipStream_t stream) {
-  if (partial == nullptr || S < 1 || M < n_seqs || !kv_scales_ok(k_scale, v_scale)) return -1;
-  QkvIn qi{static_cast<const float*>(partial), static_cast<const int*>(positions), static_cast<const float*>(cos_sin),
-           static_cast<const int*>(slots), S, M};
-  const KvScale ks{k_scale, v_scale};
-  return decode_launch(out, nullptr, qi, k_cache, v_cache, block_tables, context_lens, part_o, part_ml,
-                       n_seqs, n_q, n_kv, bs, max_blocks, 0, out_stride, scale, max_ctx, stream, &ks);
-}
-
-int pk_get_decode_z() { return g_decode_z; }  // the fused QKV -> attention launch (decode_fused.hip)
-
-PK_EXPORT int pk_set_decode_z(int z) {
-  if (z < 1) return -1;
-  g_decode_z = z;
-  return 0;
+  const QkvIn qi{static_cast<const float*>(partial), static_cast<const int*>(positions),
+                 static_cast<const float*>(cos_sin), static_cast<const int*>(slots), S, M};
+  return decode_launch(out, nullptr, qi, k_cache, v_cache, block_tables, context_lens, part_o, part_ml, n_seqs, n_q,
+                       n_kv, bs, max_blocks, 0, out_stride, scale, max_ctx, kv_dtype, k_scale, v_scale, stream);
 }
 
 // CT: cache element type; v_scale: none (bf16) or the V scale (FP8, `scale` then carries the K scale)
@@ -540,21 +505,14 @@ static int prefill_launch(void* out, const void* q, const void* k_cache, const v
   return PK_CHECK_LAUNCH();
 }
 
+// Varlen causal prefill over the paged cache, every GQA group size for either cache type.
 PK_EXPORT int pk_paged_prefill(void* out, const void* q, const void* k_cache, const void* v_cache,
-                               const void* block_tables, const void* context_lens, const void* cu_q, void* unused,
-                               int n_seqs, int n_q, int n_kv, int bs, int max_blocks, int q_stride, int out_stride,
-                               int max_q_len, float scale, hipStream_t stream) {
-  return prefill_launch<bf16_t>(out, q, k_cache, v_cache, block_tables, context_lens, cu_q, n_seqs, n_q, n_kv, bs,
-                                max_blocks, q_stride, out_stride, max_q_len, scale, stream);
-}
-
-// Prefill over an FP8 (e4m3) cache, every GQA group size of the bf16 entry point.
-PK_EXPORT int pk_paged_prefill_fp8(void* out, const void* q, const void* k_cache, const void* v_cache,
-                                   const void* block_tables, const void* context_lens, const void* cu_q,
-                                   int n_seqs, int n_q, int n_kv, int bs, int max_blocks, int q_stride,
-                                   int out_stride, int max_q_len, float scale, float k_scale, float v_scale,
-                                   hipStream_t stream) {
-  if (!kv_scales_ok(k_scale, v_scale)) return -1;
-  return prefill_launch<fp8_t>(out, q, k_cache, v_cache, block_tables, context_lens, cu_q, n_seqs, n_q, n_kv, bs,
-                               max_blocks, q_stride, out_stride, max_q_len, scale * k_scale, stream, v_scale);
+                               const void* block_tables, const void* context_lens, const void* cu_q, int n_seqs,
+                               int n_q, int n_kv, int bs, int max_blocks, int q_stride, int out_stride, int max_q_len,
+                               float scale, int kv_dtype, float k_scale, float v_scale, hipStream_t stream) {
+  return with_kv_type(kv_dtype, k_scale, v_scale, [&](auto ct, auto... sc) {
+    return prefill_launch<decltype(ct)>(out, q, k_cache, v_cache, block_tables, context_lens, cu_q, n_seqs, n_q,
+                                        n_kv, bs, max_blocks, q_stride, out_stride, max_q_len, (scale * ... * sc.k),
+                                        stream, sc.v...);
+  });
 }

@@ -7,6 +7,21 @@
 
 using namespace pk;
 
+// The launch plan of decode attention, shared by the decode entry points (attention.hip, which
+// defines the two functions) and the fused QKV -> attention launch (decode_fused.hip).
+struct DecodePlan {
+  int part;     // keys per partition: kDecodePart or kDecodePartSmall
+  int n_parts;  // partitions of the launch's context bound (the stride of the partial slabs)
+  int z;        // grid z: partition workgroups per (seq, kv head)
+};
+// Checks the shape, clamps max_ctx (<= 0: the block-table capacity) and fills the plan.
+// 0, -1 (unsupported shape) or -2 (more than one partition and no partial slabs).
+int decode_plan(DecodePlan& plan, int n_seqs, int n_q, int n_kv, int bs, int max_blocks, int max_ctx,
+                const void* part_o, const void* part_ml);
+// Launches the merge kernel of a plan with more than one partition (else nothing); 0 or a HIP error.
+int decode_merge(const DecodePlan& plan, void* out, const void* part_o, const void* part_ml,
+                 const void* context_lens, int n_seqs, int n_q, int out_stride, hipStream_t stream);
+
 namespace {
 
 constexpr int kHD = 128;
@@ -14,12 +29,8 @@ constexpr int kStep = 32;
 constexpr float kLog2e = 1.4426950408889634f;
 constexpr float kNegBig = -1e30f;
 constexpr int kDecodeWaves = 4;  // waves per (seq, kv head, partition); 8 measured ~10 % slower at 384 keys
+constexpr int kDecodePart = 512;       // keys per decode partition (ops/attention.py _PART must match)
 constexpr int kDecodePartSmall = 128;  // keys per partition when (seq, kv head) pairs cannot fill the chip
-// ... i.e. fewer workgroups than this at the full partition (pk_set_decode_fill).  64: the 70B TP=8
-// rank's 64 sequences x 1 kv head stay at 512 keys (one workgroup per sequence, no merge launch):
-// per-rank step 6.52 vs 6.54 ms at 256 (128-key partitions + merge), profiles/r5_attn_ab4.jsonl
-int g_decode_fill = 64;
-int g_decode_z = 4;  // max partition workgroups per (seq, kv head) (pk_set_decode_z)
 // (8-wave workgroups for small launches, pk_set_decode_wide: within noise at the 70B TP=8 shard,
 // profiles/r5_wide_attn.jsonl -- removed in round 6)
 

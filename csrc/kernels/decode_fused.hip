@@ -16,9 +16,6 @@
 
 using namespace pk;
 
-int pk_get_decode_z();                          // attention.hip
-int decode_part(int n_seqs, int n_kv, int max_ctx);  // attention.hip: keys per partition (512 or 128)
-
 namespace {
 
 struct AttnArgs {
@@ -78,14 +75,11 @@ PK_EXPORT int pk_qkv_attn_fused(const GemmArgs* qkv_in, void* out, const void* p
   // up to 128 rows (one row tile; 128 rows take the MT = 8 tile, whose row scale reads <= 16 parts)
   if (n_seqs > 128 || (n_seqs > 64 && g.nrm_nparts > 16) || g.N != (n_q + 2 * n_kv) * kHD || g.N % 128 || g.S < 1 || g.K % (kKC * g.S) || !g.row_scale ||
       g.nrm_parts == nullptr || g.nrm_nparts < 1 || g.nrm_nparts > 64 || g.partial == nullptr || g.lda % 8 ||
-      g.row_offsets != nullptr || n_kv > 64 || n_q % n_kv || n_q / n_kv > 16 || bs % 32 || bs <= 0 ||
-      flow == nullptr)  // n_kv <= 64: one ticket slot per kv head below the done counters
+      g.row_offsets != nullptr || n_kv > 64 || flow == nullptr)  // n_kv <= 64: one ticket slot per kv head below the done counters
     return -1;
-  if (max_ctx <= 0 || max_ctx > max_blocks * bs) max_ctx = max_blocks * bs;
-  const int P = decode_part(n_seqs, n_kv, max_ctx);  // 128-key partitions when the pairs alone cannot fill the chip
-  const int n_parts = (max_ctx + P - 1) / P;
-  if (n_parts > 1 && (part_o == nullptr || part_ml == nullptr)) return -2;
-  const int z = n_parts < pk_get_decode_z() ? n_parts : pk_get_decode_z();
+  DecodePlan plan;  // 128-key partitions when the pairs alone cannot fill the chip
+  if (const int rc = decode_plan(plan, n_seqs, n_q, n_kv, bs, max_blocks, max_ctx, part_o, part_ml)) return rc;
+  const int z = plan.z;
   g.row_tiles = 1;
   g.tile_rows = n_seqs > 64 ? 128 : 64;
   g.max_group_rows = 0;
@@ -94,7 +88,7 @@ PK_EXPORT int pk_qkv_attn_fused(const GemmArgs* qkv_in, void* out, const void* p
   const AttnArgs aa{static_cast<bf16_t*>(out), static_cast<bf16_t*>(k_cache), static_cast<bf16_t*>(v_cache),
                     static_cast<const int*>(block_tables), static_cast<const int*>(context_lens),
                     static_cast<float*>(part_o), static_cast<float*>(part_ml), n_q, n_kv, bs, max_blocks, out_stride,
-                    n_parts, n_seqs, z, scale * 1.4426950408889634f, qi};
+                    plan.n_parts, n_seqs, z, scale * kLog2e, qi};
   int* done = flow + 64 * kFlowPad;
   int* err = fused_err_word() != nullptr ? fused_err_word() : flow + 128 * kFlowPad;
   const int G = n_q / n_kv;
@@ -106,10 +100,10 @@ PK_EXPORT int pk_qkv_attn_fused(const GemmArgs* qkv_in, void* out, const void* p
   const dim3 grid(n_attn > n_qkv ? n_attn : n_qkv);
   auto go = [&](auto mt, auto ss) {
     constexpr int MT = decltype(mt)::value, SS = decltype(ss)::value;
-    if (P == kDecodePartSmall)
+    if (plan.part == kDecodePartSmall)
       qkv_attn_fused_kernel<MT, SS, kDecodePartSmall><<<grid, 256, 0, stream>>>(g, aa, fq, fa, n_qkv, n_attn);
     else
-      qkv_attn_fused_kernel<MT, SS, 512><<<grid, 256, 0, stream>>>(g, aa, fq, fa, n_qkv, n_attn);
+      qkv_attn_fused_kernel<MT, SS, kDecodePart><<<grid, 256, 0, stream>>>(g, aa, fq, fa, n_qkv, n_attn);
   };
   auto go_mt = [&](auto ss) {
     switch ((n_seqs + 15) / 16) {
@@ -128,15 +122,6 @@ PK_EXPORT int pk_qkv_attn_fused(const GemmArgs* qkv_in, void* out, const void* p
     case 16: go_mt(std::integral_constant<int, 16>{}); break;
     default: go_mt(std::integral_constant<int, 0>{}); break;
   }
-  int rc = PK_CHECK_LAUNCH();
-  if (rc || n_parts == 1) return rc;
-  if (P == kDecodePartSmall)
-    paged_decode_reduce_kernel<kDecodePartSmall><<<dim3(n_q, n_seqs), 128, 0, stream>>>(
-        static_cast<bf16_t*>(out), static_cast<const float*>(part_o), static_cast<const float*>(part_ml),
-        static_cast<const int*>(context_lens), n_q, out_stride, n_parts, z);
-  else
-    paged_decode_reduce_kernel<512><<<dim3(n_q, n_seqs), 128, 0, stream>>>(
-        static_cast<bf16_t*>(out), static_cast<const float*>(part_o), static_cast<const float*>(part_ml),
-        static_cast<const int*>(context_lens), n_q, out_stride, n_parts, z);
-  return PK_CHECK_LAUNCH();
+  const int rc = PK_CHECK_LAUNCH();
+  return rc ? rc : decode_merge(plan, out, part_o, part_ml, context_lens, n_seqs, n_q, out_stride, stream);
 }

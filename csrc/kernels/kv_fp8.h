@@ -27,6 +27,16 @@ inline bool kv_scales_ok(float k_scale, float v_scale) {
   return k_scale > 0.f && v_scale > 0.f && k_scale < INFINITY && v_scale < INFINITY;
 }
 
+// The cache type argument of an entry point: kv_dtype 0 is bf16 (the scales are ignored), 1 is e4m3
+// with scales that pass kv_scales_ok.  Calls f(element, scales...): a bf16_t and no scales, or an
+// fp8_t and one KvScale -- the trailing pack the kernels take.  Anything else: -1, f is not called.
+template <typename F>
+int with_kv_type(int kv_dtype, float k_scale, float v_scale, F&& f) {
+  if (kv_dtype == 0) return f(bf16_t{});
+  if (kv_dtype == 1 && kv_scales_ok(k_scale, v_scale)) return f(fp8_t{}, KvScale{k_scale, v_scale});
+  return -1;
+}
+
 // x / scale clamped to the finite range (+-inf and anything beyond +-448 store +-448; the clamp is
 // explicit, the conversion's own overflow mode is never reached)
 __device__ __forceinline__ float fp8_prep(float x, float scale) {

@@ -179,4 +179,5 @@ PK_EXPORT int pk_silu_and_mul_il(void* out, const void* in, int T, int I, hipStr
   return PK_CHECK_LAUNCH();
 }
 
-PK_EXPORT int pk_kernels_abi_version() { return 1; }
+// 2: the attention and rope entry points take the cache type (kv_dtype, k_scale, v_scale)
+PK_EXPORT int pk_kernels_abi_version() { return 2; }

@@ -146,28 +146,19 @@ __global__ void __launch_bounds__(256) rope_and_cache_kernel(bf16_t* __restrict_
 
 }  // namespace
 
+// kv_dtype, k_scale, v_scale: kv_fp8.h with_kv_type.  An FP8 (e4m3) cache gets
+// byte = e4m3_rne(clamp(x / scale, -448, 448)).
 PK_EXPORT int pk_rope_and_cache(void* qkv, const void* positions, const void* cos_sin, void* k_cache, void* v_cache,
                                 const void* slot_mapping, int T, int nq, int nkv, int hd, int bs, int q_stride,
-                                int unused, hipStream_t stream) {
+                                int kv_dtype, float k_scale, float v_scale, hipStream_t stream) {
   if (T <= 0) return 0;
   if (hd != kHD || (bs % 32) != 0) return -1;  // fragment-native K tiles of 32 tokens
-  rope_and_cache_kernel<bf16_t><<<(T + kTokTile - 1) / kTokTile, 256, 0, stream>>>(
-      static_cast<bf16_t*>(qkv), static_cast<const int*>(positions), static_cast<const float*>(cos_sin),
-      static_cast<bf16_t*>(k_cache), static_cast<bf16_t*>(v_cache), static_cast<const int*>(slot_mapping), T, nq, nkv,
-      bs, q_stride);
-  return PK_CHECK_LAUNCH();
-}
-
-// The same launch writing an FP8 (e4m3) cache: byte = e4m3_rne(clamp(x / scale, -448, 448)).
-PK_EXPORT int pk_rope_and_cache_fp8(void* qkv, const void* positions, const void* cos_sin, void* k_cache, void* v_cache,
-                                    const void* slot_mapping, int T, int nq, int nkv, int hd, int bs, int q_stride,
-                                    float k_scale, float v_scale, hipStream_t stream) {
-  if (T <= 0) return 0;
-  if (hd != kHD || (bs % 32) != 0) return -1;
-  if (!kv_scales_ok(k_scale, v_scale)) return -1;
-  rope_and_cache_kernel<fp8_t><<<(T + kTokTile - 1) / kTokTile, 256, 0, stream>>>(
-      static_cast<bf16_t*>(qkv), static_cast<const int*>(positions), static_cast<const float*>(cos_sin),
-      static_cast<fp8_t*>(k_cache), static_cast<fp8_t*>(v_cache), static_cast<const int*>(slot_mapping), T, nq, nkv,
-      bs, q_stride, KvScale{k_scale, v_scale});
-  return PK_CHECK_LAUNCH();
+  return with_kv_type(kv_dtype, k_scale, v_scale, [&](auto ct, auto... sc) {
+    using CT = decltype(ct);
+    rope_and_cache_kernel<CT><<<(T + kTokTile - 1) / kTokTile, 256, 0, stream>>>(
+        static_cast<bf16_t*>(qkv), static_cast<const int*>(positions), static_cast<const float*>(cos_sin),
+        static_cast<CT*>(k_cache), static_cast<CT*>(v_cache), static_cast<const int*>(slot_mapping), T, nq, nkv, bs,
+        q_stride, sc...);
+    return PK_CHECK_LAUNCH();
+  });
 }

@@ -170,10 +170,9 @@ class LlamaAttention(nn.Module):
         T = x.shape[0]
         k_cache, v_cache = kv
         S = gemm.choose_split(self.qkv.shape[0], x.shape[1], T)
-        # (an FP8 cache has no split-K epilogue writer: its steps with prefill take linear -> rope_and_cache)
-        fp8_prefill = md.num_prefill > 0 and k_cache.dtype == attn_ops.FP8
+        # (a cache without the split-K epilogue writer: its steps with prefill take linear -> rope_and_cache)
         if (ws is not None and gemm.skinny_ok(x, self.qkv) and S > 1 and ws.numel() >= S * T * self.qkv.shape[0]
-                and not fp8_prefill):
+                and (md.num_prefill == 0 or attn_ops.slab_writers_ok(k_cache))):
             p = gemm.linear_partial(x, self.qkv, ws, S, packed=self.qkv_p)
             if md.num_prefill == 0:
                 # pure decode: the attention kernel itself reduces the QKV slabs, applies RoPE
@@ -398,8 +397,8 @@ class LlamaForCausalLM(nn.Module):
         ws = self.workspace(x.shape[0])
         # the folded chain serves decode batches up to DECODE_MAX_M rows; steps carrying prefill
         # chunks above 64 rows keep the library GEMMs (hipBLASLt) of the general path
-        fp8 = bool(kv_caches) and kv_caches[0][0].dtype == attn_ops.FP8
-        if (ws is not None and (md.num_prefill == 0 or (x.shape[0] <= gemm.SKINNY_MAX_M and not fp8))
+        writers = not kv_caches or attn_ops.slab_writers_ok(kv_caches[0][0])
+        if (ws is not None and (md.num_prefill == 0 or (x.shape[0] <= gemm.SKINNY_MAX_M and writers))
                 and self._rowscale_ok(x)):
             return self._forward_rowscale(x, positions, md, kv_caches, ws)
         residual = None
@@ -516,10 +515,8 @@ class LlamaForCausalLM(nn.Module):
     def _qkv_attn_fused_ok(self, at, T: int, nparts: int, md, kc: Optional[torch.Tensor] = None) -> bool:
         # (a TP rank sharing its GPU keeps the two launches: a hand-off lost to a co-tenant has a
         # fallback only at TP = 1 -- a TP group cannot re-run one rank's step, llm_engine.py)
-        # kc: the K cache the step writes.  The launch is bf16-only, like the split-K QKV epilogue
-        # writer and the carried TP collective: an FP8 (e4m3) cache bypasses all three, decided
-        # from the dtype of the cache at hand and nothing else.
-        if kc is not None and kc.dtype == attn_ops.FP8:
+        # kc: the K cache the step writes (ops/attention.py slab_writers_ok)
+        if kc is not None and not attn_ops.slab_writers_ok(kc):
             return False
         return (md.num_prefill == 0 and gemm.QKV_ATTN_FUSED and at.nkv >= gemm.QKV_ATTN_MIN_KV
                 and gemm.fused_rows_ok(T, nparts) and md.num_decode == T
@@ -545,7 +542,7 @@ class LlamaForCausalLM(nn.Module):
         if md.num_prefill == 0:
             return attn_ops.paged_decode_from_qkv(p, positions, self.cos_sin, kc, vc, md, at.scale, at.nq, at.nkv,
                                                   k_scale=at.k_scale, v_scale=at.v_scale)
-        assert kc.dtype != attn_ops.FP8, "FP8 KV cache: steps with prefill take the general path (forward)"
+        # (asserts slab_writers_ok: an FP8 cache's steps with prefill take the general path, forward)
         q = gemm.qkv_reduce_rope_cache(p, positions, self.cos_sin, kc, vc, md.slot_mapping, at.nq, at.nkv)
         return attn_ops.paged_attention(q, kc, vc, md, at.scale)
 
@@ -632,7 +629,7 @@ class LlamaForCausalLM(nn.Module):
         on = self.carry_collectives
         if on is None:
             on = os.environ.get("POLYKEY_TP_CARRY", "0") in ("1", "gate_up") and not self.st.shared_device
-        if on and kc is not None and kc.dtype == attn_ops.FP8:
+        if on and kc is not None and not attn_ops.slab_writers_ok(kc):
             if not LlamaForCausalLM._carry_warned:
                 LlamaForCausalLM._carry_warned = True
                 logging.getLogger(__name__).warning(

@@ -39,21 +39,22 @@ class AttnMetadata:
         return self.num_decode + self.num_prefill_tokens
 
 
-_PART = 512  # must match kDecodePart in csrc/kernels/attention.hip
+_PART = 512  # must match kDecodePart in csrc/kernels/attn_decode.h
 _PART_MIN = 128  # kDecodePartSmall: launches whose (seq, kv head) pairs cannot fill the chip
 _FILL_SET = False
 
 
 def apply_decode_fill() -> None:
     """POLYKEY_DECODE_FILL, applied once per process: the workgroup count below which decode
-    attention takes 128-key partitions (csrc attention.hip decode_part; 0: always 512)."""
+    attention takes 128-key partitions (csrc attention.hip decode_plan; 0: always 512)."""
     global _FILL_SET
     if not _FILL_SET and os.environ.get("POLYKEY_DECODE_FILL") is not None:
         native.call("pk_set_decode_fill", int(os.environ["POLYKEY_DECODE_FILL"]))
     _FILL_SET = True
 
 
-# g_decode_fill (csrc attn_decode.h): fewer (seq, kv head, partition) workgroups than this -> 128-key partitions
+# g_decode_fill (csrc attention.hip): fewer (seq, kv head, partition) workgroups than this -> 128-key partitions.
+# The library's own default is 64: sizing the slabs for 256 only over-allocates them.
 _DECODE_FILL = int(os.environ.get("POLYKEY_DECODE_FILL", "256"))
 
 
@@ -62,7 +63,7 @@ def decode_workspace(n_seqs: int, n_q: int, max_blocks: int, block_size: int, de
     """Partition slabs for split-K decode attention.  A launch
     strides the slabs by its OWN partition count, so they are sized for the largest launch:
     ``n_seqs`` sequences at 512-key partitions, or the few sequences that take 128-key ones
-    (csrc attention.hip decode_part: fewer than 256 (seq, kv head) workgroups, i.e. at most
+    (csrc attention.hip decode_plan: fewer than 256 (seq, kv head) workgroups, i.e. at most
     255 // kv_heads sequences).  ``kv_heads`` (kv heads per rank; else ``n_kv``) None: every
     launch sized at 128-key partitions (4x the full-batch need: ~4.3 GB at 256 seqs x 128k ctx
     for Llama-3-8B, taken from the KV-cache budget -- ADVICE r4)."""
@@ -85,7 +86,7 @@ FP8 = reference.FP8  # the reduced-precision KV-cache element (OCP e4m3, csrc/ke
 
 
 def cache_is_fp8(k_cache: torch.Tensor, v_cache: torch.Tensor) -> bool:
-    """Which kernel family a layer's caches take: bf16 or FP8 (e4m3).  K and V of one layer share
+    """Which cache type a layer's launches are told: bf16 or FP8 (e4m3).  K and V of one layer share
     the dtype; anything else is an error, never a silent conversion."""
     if k_cache.dtype != v_cache.dtype:
         raise TypeError(f"K and V cache dtypes differ: {k_cache.dtype} vs {v_cache.dtype}")
@@ -94,6 +95,20 @@ def cache_is_fp8(k_cache: torch.Tensor, v_cache: torch.Tensor) -> bool:
     if k_cache.dtype != torch.bfloat16:
         raise TypeError(f"unsupported KV-cache dtype {k_cache.dtype}: bfloat16 or float8_e4m3fn")
     return False
+
+
+def _kv_args(k_cache: torch.Tensor, v_cache: torch.Tensor, k_scale: float, v_scale: float) -> tuple:
+    """``kv_dtype, k_scale, v_scale``: what every attention entry point takes ahead of the stream."""
+    return int(cache_is_fp8(k_cache, v_cache)), float(k_scale), float(v_scale)
+
+
+def slab_writers_ok(k_cache: torch.Tensor) -> bool:
+    """Whether the launches that write k / v rows from the QKV projection's fp32 slabs may serve this
+    cache.  Three launches are bf16-only (2-byte rows): the split-K QKV epilogue writer
+    (``gemm.qkv_reduce_rope_cache``), the fused QKV -> attention launch (``gemm.qkv_attn_fused``)
+    and the carried TP collective (``LlamaForCausalLM._forward_tp_carried``).  An FP8 (e4m3) cache
+    bypasses all three, decided from the dtype of the cache at hand and nothing else."""
+    return k_cache.dtype == torch.bfloat16
 
 
 def rope_and_cache(qkv: torch.Tensor, positions: torch.Tensor, cos_sin: torch.Tensor, k_cache: torch.Tensor,
@@ -108,14 +123,9 @@ def rope_and_cache(qkv: torch.Tensor, positions: torch.Tensor, cos_sin: torch.Te
     T = qkv.shape[0]
     assert qkv.stride(-1) == 1 and positions.dtype == torch.int32 and slot_mapping.dtype == torch.int32
     assert cos_sin.dtype == torch.float32
-    if cache_is_fp8(k_cache, v_cache):
-        native.call("pk_rope_and_cache_fp8", qkv.data_ptr(), positions.data_ptr(), cos_sin.data_ptr(),
-                    k_cache.data_ptr(), v_cache.data_ptr(), slot_mapping.data_ptr(), T, nq, nkv, hd, k_cache.shape[2],
-                    qkv.stride(0), float(k_scale), float(v_scale), native.stream_ptr())
-        return
     native.call("pk_rope_and_cache", qkv.data_ptr(), positions.data_ptr(), cos_sin.data_ptr(), k_cache.data_ptr(),
-                v_cache.data_ptr(), slot_mapping.data_ptr(), T, nq, nkv, hd, k_cache.shape[2], qkv.stride(0), 0,
-                native.stream_ptr())
+                v_cache.data_ptr(), slot_mapping.data_ptr(), T, nq, nkv, hd, k_cache.shape[2], qkv.stride(0),
+                *_kv_args(k_cache, v_cache, k_scale, v_scale), native.stream_ptr())
 
 
 def paged_attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, md: AttnMetadata,
@@ -134,40 +144,24 @@ def paged_attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tenso
         return out
     assert hd == 128 and q.stride(-1) == 1 and q.stride(1) == hd
     apply_decode_fill()
+    kv = _kv_args(k_cache, v_cache, k_scale, v_scale)
     stream = native.stream_ptr()
     nd = md.num_decode
-    if cache_is_fp8(k_cache, v_cache):
-        if nd > 0:
-            bt = md.decode_block_tables
-            native.call("pk_paged_decode_fp8", out.data_ptr(), q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(),
-                        bt.data_ptr(), md.decode_context_lens.data_ptr(),
-                        native.ptr(md.decode_part_o) or 0, native.ptr(md.decode_part_ml) or 0,
-                        nd, nq, nkv, bs, bt.stride(0), q.stride(0), out.stride(0),
-                        float(scale), int(md.decode_max_ctx), float(k_scale), float(v_scale), stream)
-        if md.num_prefill > 0:
-            bt = md.prefill_block_tables
-            qp = q[nd:]
-            op = out[nd:]
-            native.call("pk_paged_prefill_fp8", op.data_ptr(), qp.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(),
-                        bt.data_ptr(), md.prefill_context_lens.data_ptr(), md.prefill_cu_q.data_ptr(),
-                        md.num_prefill, nq, nkv, bs, bt.shape[1], q.stride(0), out.stride(0),
-                        int(md.max_prefill_q_len), float(scale), float(k_scale), float(v_scale), stream)
-        return out
     if nd > 0:
         bt = md.decode_block_tables
         native.call("pk_paged_decode", out.data_ptr(), q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(),
                     bt.data_ptr(), md.decode_context_lens.data_ptr(),
                     native.ptr(md.decode_part_o) or 0, native.ptr(md.decode_part_ml) or 0,
                     nd, nq, nkv, bs, bt.stride(0), q.stride(0), out.stride(0),
-                    float(scale), int(md.decode_max_ctx), stream)
+                    float(scale), int(md.decode_max_ctx), *kv, stream)
     if md.num_prefill > 0:
         bt = md.prefill_block_tables
         qp = q[nd:]
         op = out[nd:]
         native.call("pk_paged_prefill", op.data_ptr(), qp.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(),
-                    bt.data_ptr(), md.prefill_context_lens.data_ptr(), md.prefill_cu_q.data_ptr(), 0,
+                    bt.data_ptr(), md.prefill_context_lens.data_ptr(), md.prefill_cu_q.data_ptr(),
                     md.num_prefill, nq, nkv, bs, bt.shape[1], q.stride(0), out.stride(0), int(md.max_prefill_q_len),
-                    float(scale), stream)
+                    float(scale), *kv, stream)
     return out
 
 
@@ -200,17 +194,10 @@ def paged_decode_from_qkv(p, positions: torch.Tensor, cos_sin: torch.Tensor, k_c
     T = p.M
     out = torch.empty((T, nq * 128), dtype=torch.bfloat16, device=p.buf.device)
     bt = md.decode_block_tables
-    if cache_is_fp8(k_cache, v_cache):
-        native.call("pk_paged_decode_qkv_fp8", out.data_ptr(), p.buf.data_ptr(), p.S, p.M, positions.data_ptr(),
-                    cos_sin.data_ptr(), md.slot_mapping.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(),
-                    bt.data_ptr(), md.decode_context_lens.data_ptr(), native.ptr(md.decode_part_o) or 0,
-                    native.ptr(md.decode_part_ml) or 0, md.num_decode, nq, nkv, k_cache.shape[2], bt.stride(0),
-                    out.stride(0), float(scale), int(md.decode_max_ctx), float(k_scale), float(v_scale),
-                    native.stream_ptr())
-        return out
     native.call("pk_paged_decode_qkv", out.data_ptr(), p.buf.data_ptr(), p.S, p.M, positions.data_ptr(),
                 cos_sin.data_ptr(), md.slot_mapping.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(),
                 bt.data_ptr(), md.decode_context_lens.data_ptr(), native.ptr(md.decode_part_o) or 0,
                 native.ptr(md.decode_part_ml) or 0, md.num_decode, nq, nkv, k_cache.shape[2], bt.stride(0),
-                out.stride(0), float(scale), int(md.decode_max_ctx), native.stream_ptr())
+                out.stride(0), float(scale), int(md.decode_max_ctx), *_kv_args(k_cache, v_cache, k_scale, v_scale),
+                native.stream_ptr())
     return out

@@ -17,6 +17,7 @@ import torch
 import torch.nn.functional as F
 
 from . import native, reference
+from .attention import slab_writers_ok
 
 import os
 
@@ -648,7 +649,7 @@ def qkv_attn_fused(x: torch.Tensor, qkv_packed: torch.Tensor, rowscale: RowScale
     reduces them, applies RoPE, writes the new k / v to the paged cache and attends.  Same
     result as :func:`linear_partial_rowscale` + ``attention.paged_decode_from_qkv``.  ``flow``:
     int32 >= :data:`FLOW_WORDS`, zeroed once, left zeroed.  Returns [M, nq * 128] bf16."""
-    assert k_cache.dtype == torch.bfloat16 and v_cache.dtype == torch.bfloat16, "bf16 caches only (2-byte rows)"
+    assert slab_writers_ok(k_cache) and slab_writers_ok(v_cache), "bf16 caches only (2-byte rows)"
     M, K = x.shape
     N = qkv_packed.shape[0]
     S = S or choose_split(N, K, M)
@@ -755,7 +756,7 @@ def silu_and_mul_interleaved(x: torch.Tensor, out: Optional[torch.Tensor] = None
 def qkv_reduce_rope_cache(p: Partial, positions: torch.Tensor, cos_sin: torch.Tensor, k_cache: torch.Tensor,
                           v_cache: torch.Tensor, slots: torch.Tensor, nq: int, nkv: int) -> torch.Tensor:
     """Split-K QKV epilogue: sum slabs, RoPE q/k, write k/v to the paged cache → q [M, nq, 128]."""
-    assert k_cache.dtype == torch.bfloat16 and v_cache.dtype == torch.bfloat16, "bf16 caches only (2-byte rows)"
+    assert slab_writers_ok(k_cache) and slab_writers_ok(v_cache), "bf16 caches only (2-byte rows)"
     q = torch.empty((p.M, nq, 128), dtype=torch.bfloat16, device=p.buf.device)
     native.call("pk_qkv_reduce_rope_cache", q.data_ptr(), p.buf.data_ptr(), p.S, p.M, nq, nkv, positions.data_ptr(),
                 cos_sin.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), slots.data_ptr(), k_cache.shape[2],

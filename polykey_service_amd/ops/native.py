@@ -27,25 +27,22 @@ P = ctypes.c_void_p
 I32 = ctypes.c_int
 I64 = ctypes.c_int64
 F32 = ctypes.c_float
+KV = (I32, F32, F32)  # kv_dtype, k_scale, v_scale
 
-# name -> argtypes (restype is always c_int)
+# name -> argtypes (restype is always c_int); tests/unit/test_native_signatures.py holds them against
+# the PK_EXPORT declarations in csrc/kernels
 SIGNATURES = {
     "pk_kernels_abi_version": [],
     "pk_rmsnorm": [P, P, P, I32, I32, I32, I32, F32, P],
     "pk_fused_add_rmsnorm": [P, P, P, I32, I32, F32, P],
     "pk_silu_and_mul": [P, P, I32, I32, P],
-    "pk_rope_and_cache": [P, P, P, P, P, P, I32, I32, I32, I32, I32, I32, I32, P],
-    "pk_paged_decode": [P, P, P, P, P, P, P, P, I32, I32, I32, I32, I32, I32, I32, F32, I32, P],
+    # the four attention launches end in kv_dtype (0: bf16, 1: e4m3 byte caches), k_scale, v_scale, stream
+    "pk_rope_and_cache": [P, P, P, P, P, P, I32, I32, I32, I32, I32, I32, *KV, P],
+    "pk_paged_decode": [P, P, P, P, P, P, P, P, I32, I32, I32, I32, I32, I32, I32, F32, I32, *KV, P],
     "pk_set_decode_z": [I32],
     "pk_set_decode_fill": [I32],
-    "pk_paged_decode_qkv": [P, P, I32, I32, P, P, P, P, P, P, P, P, P, I32, I32, I32, I32, I32, I32, F32, I32, P],
-    "pk_paged_prefill": [P, P, P, P, P, P, P, P, I32, I32, I32, I32, I32, I32, I32, I32, F32, P],
-    # FP8 (e4m3) KV cache: the same launches over byte caches + k_scale, v_scale
-    "pk_rope_and_cache_fp8": [P, P, P, P, P, P, I32, I32, I32, I32, I32, I32, F32, F32, P],
-    "pk_paged_decode_fp8": [P, P, P, P, P, P, P, P, I32, I32, I32, I32, I32, I32, I32, F32, I32, F32, F32, P],
-    "pk_paged_decode_qkv_fp8": [P, P, I32, I32, P, P, P, P, P, P, P, P, P, I32, I32, I32, I32, I32, I32, F32, I32,
-                                F32, F32, P],
-    "pk_paged_prefill_fp8": [P, P, P, P, P, P, P, I32, I32, I32, I32, I32, I32, I32, I32, F32, F32, F32, P],
+    "pk_paged_decode_qkv": [P, P, I32, I32, P, P, P, P, P, P, P, P, P, I32, I32, I32, I32, I32, I32, F32, I32, *KV, P],
+    "pk_paged_prefill": [P, P, P, P, P, P, P, I32, I32, I32, I32, I32, I32, I32, I32, F32, *KV, P],
     "pk_sample": [P, P, P, P, P, P, P, P, P, I32, I32, I32, I32, P],
     "pk_sample_alt": [P, P, P, P, P, P, P, P, I32, I32, I32, I32, P, I64, P, I32, P],
     "pk_logprobs": [P, P, P, P, I32, I32, I32, I32, P],

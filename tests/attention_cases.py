@@ -36,7 +36,7 @@ SCALE = 1.0 / math.sqrt(HD)
 POISON_V = 2.0 ** 100
 LOUD_K = 2.0 ** 10
 MAX_NEEDLES = 8
-DECODE_FILL = 64        # csrc/kernels/attn_decode.h g_decode_fill
+DECODE_FILL = 64        # csrc/kernels/attention.hip g_decode_fill
 DECODE_Z = 4            # g_decode_z
 PART, PART_SMALL = 512, 128
 
@@ -279,7 +279,7 @@ def check(out, ref: Ref, what=""):
 
 # ---------------------------------------------------------------- decode: dispatch and cases
 def decode_dispatch(n_seqs: int, nkv: int, max_ctx: int):
-    """csrc/kernels/attention.hip decode_part + decode_launch_p, at the default fill 64 and
+    """csrc/kernels/attention.hip decode_plan, at the default fill 64 and
     z cap 4 -> (keys per partition, n_parts, grid z)."""
     big = (max_ctx + PART - 1) // PART
     part = PART_SMALL if n_seqs * nkv * min(big, DECODE_Z) < DECODE_FILL else PART

@@ -244,3 +244,42 @@ def test_mismatched_cache_dtypes_are_an_error():
     md = A.AttnMetadata(num_decode=0, slot_mapping=torch.zeros(case.q.shape[0], dtype=I32, device=D), **prefill_md(case))
     with pytest.raises(TypeError):
         A.paged_attention(wide_q(case), f.kc8.to(D), case.vc.to(D), md, ac.SCALE)
+
+
+BAD_KV = [(2, 1.0, 1.0), (1, 0.0, 1.0), (1, float("inf"), 1.0), (1, float("nan"), 1.0), (1, 1.0, -1.0)]
+
+
+@pytest.mark.parametrize("kv_dtype,ks,vs", BAD_KV)
+def test_entry_points_refuse_a_bad_cache_type_before_launching(kv_dtype, ks, vs):
+    """Each of the four entry points, called as ops/attention.py calls it at the smallest legal
+    shape (1 sequence, nq = nkv = 1, one block of 32, context 1), returns -1 for an unknown
+    kv_dtype or an FP8 scale that is not positive and finite, and launches nothing: the marker in
+    the output (for rope_and_cache, the qkv rows it rotates in place) and the cache bytes stay."""
+    from polykey_service_amd.ops import native
+    marker = lambda *shape: torch.full(shape, 0x7E, dtype=torch.uint8, device=D)
+    out, qkv = marker(1, 2 * HD), marker(1, 3 * 2 * HD)                       # bf16 rows
+    kc, vc = marker(1, 1, 32, 2 * HD), marker(1, 1, HD, 2 * 32)               # room for either element type
+    q = torch.zeros(1, HD, dtype=torch.bfloat16, device=D)
+    slab = torch.zeros(1, 1, 3 * HD, device=D)                                # S = 1, M = 1
+    zero, one = torch.zeros(1, dtype=I32, device=D), torch.ones(1, dtype=I32, device=D)   # positions / slots / table; context
+    cu = torch.tensor([0, 1], dtype=I32, device=D)
+    cs = torch.zeros(1, HD, device=D)
+    kv, st = (kv_dtype, ks, vs), native.stream_ptr()
+    calls = {
+        "pk_rope_and_cache": (qkv.data_ptr(), zero.data_ptr(), cs.data_ptr(), kc.data_ptr(), vc.data_ptr(),
+                              zero.data_ptr(), 1, 1, 1, HD, 32, 3 * HD, *kv, st),
+        "pk_paged_decode": (out.data_ptr(), q.data_ptr(), kc.data_ptr(), vc.data_ptr(), zero.data_ptr(), one.data_ptr(),
+                            0, 0, 1, 1, 1, 32, 1, HD, HD, ac.SCALE, 0, *kv, st),
+        "pk_paged_decode_qkv": (out.data_ptr(), slab.data_ptr(), 1, 1, zero.data_ptr(), cs.data_ptr(), zero.data_ptr(),
+                                kc.data_ptr(), vc.data_ptr(), zero.data_ptr(), one.data_ptr(), 0, 0, 1, 1, 1, 32, 1,
+                                HD, ac.SCALE, 0, *kv, st),
+        "pk_paged_prefill": (out.data_ptr(), q.data_ptr(), kc.data_ptr(), vc.data_ptr(), zero.data_ptr(), one.data_ptr(),
+                             cu.data_ptr(), 1, 1, 1, 32, 1, HD, HD, 1, ac.SCALE, *kv, st),
+    }
+    for name, args in calls.items():
+        assert len(args) == len(native.SIGNATURES[name]), name
+        with pytest.raises(native.KernelError, match="code -1"):
+            native.call(name, *args)
+    torch.cuda.synchronize()
+    for t in (out, qkv, kc, vc):
+        assert bool((t == 0x7E).all())

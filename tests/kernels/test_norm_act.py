@@ -42,7 +42,7 @@ def test_silu_and_mul(T, I):
 
 def test_native_library_is_loaded():
     from polykey_service_amd.ops import native
-    assert native.lib().pk_kernels_abi_version() == 1
+    assert native.lib().pk_kernels_abi_version() == 2
     with open("/proc/self/maps") as f:
         assert "libpk_kernels.so" in f.read()
 

@@ -14,18 +14,15 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 
-from polykey_service_amd.ops import reference  # noqa: E402
+from polykey_service_amd.ops import native, reference  # noqa: E402
 
-P, I32, F32 = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def load(tag):
     lib = ctypes.CDLL(os.path.join(ROOT, "labbin", f"libattn_{tag}.so"))
-    f = lib.pk_paged_decode
-    f.argtypes = [P, P, P, P, P, P, P, P, P, I32, I32, I32, I32, I32, I32, I32, F32, I32, P]
-    g = lib.pk_paged_decode_qkv
-    g.argtypes = [P, P, I32, I32, P, P, P, P, P, P, P, P, P, I32, I32, I32, I32, I32, I32, F32, I32, P]
+    f, g = lib.pk_paged_decode, lib.pk_paged_decode_qkv
+    f.argtypes, g.argtypes = native.SIGNATURES["pk_paged_decode"], native.SIGNATURES["pk_paged_decode_qkv"]
     return f, g
 
 
@@ -62,19 +59,18 @@ def main():
         # split-partition builds (PK_DECODE_PART < 512) need the partial buffers; q path merges in-launch
         part_o = torch.empty(B * NQ * 8 * D, device="cuda")
         part_ml = torch.empty(B * NQ * 8 * 2, device="cuda")
-        ctrs = torch.zeros(B * NKV, dtype=torch.int32, device="cuda")
 
         def call_q(f, i):
             k, v = layers[i % 4]
             rc = f(out.data_ptr(), q.data_ptr(), k.data_ptr(), v.data_ptr(), bt.data_ptr(), cl.data_ptr(), part_o.data_ptr(),
-                   part_ml.data_ptr(), ctrs.data_ptr(), B, NQ, NKV, BS, maxb, NQ * D, NQ * D, 0.088, 512, st())
+                   part_ml.data_ptr(), B, NQ, NKV, BS, maxb, NQ * D, NQ * D, 0.088, 512, 0, 1.0, 1.0, st())
             assert rc == 0, rc
 
         def call_qkv(g_, i):
             k, v = layers[i % 4]
             rc = g_(out.data_ptr(), slab.data_ptr(), 4, B, pos.data_ptr(), cs.data_ptr(), slots.data_ptr(),
                     k.data_ptr(), v.data_ptr(), bt.data_ptr(), cl.data_ptr(), part_o.data_ptr(), part_ml.data_ptr(), B, NQ, NKV, BS, maxb,
-                    NQ * D, 0.088, 512, st())
+                    NQ * D, 0.088, 512, 0, 1.0, 1.0, st())
             assert rc == 0, rc
 
         def timeit(fn):

@@ -48,7 +48,7 @@ __global__ void __launch_bounds__(256, 2) qa_stamped(const GemmArgs qkv, const A
   if (b < n_attn) {
     const int x = b % aa.n_kv, y = (b / aa.n_kv) % aa.n_seqs, z = b / (aa.n_kv * aa.n_seqs);
     decode_tile<P, kDecodeWaves, true, SS, 2, PRE>(
-        aa.out, nullptr, aa.kc, aa.vc, aa.block_tables, aa.context_lens, aa.part_o, aa.part_ml, nullptr, aa.n_q,
+        aa.out, nullptr, aa.kc, aa.vc, aa.block_tables, aa.context_lens, aa.part_o, aa.part_ml, aa.n_q,
         aa.n_kv, aa.bs, aa.max_blocks, 0, aa.out_stride, aa.n_parts, aa.scale2, aa.qi, x, y, z, aa.z, lds.a, fa);
   }
   __syncthreads();
@@ -81,7 +81,7 @@ extern "C" int qa_stamped_launch(const GemmArgs* qkv_in, void* out, const void* 
                  static_cast<const float*>(cos_sin), static_cast<const int*>(slots), g.S, g.M};
   const AttnArgs aa{static_cast<bf16_t*>(out), static_cast<bf16_t*>(k_cache), static_cast<bf16_t*>(v_cache),
                     static_cast<const int*>(block_tables), static_cast<const int*>(context_lens), nullptr, nullptr,
-                    n_q, n_kv, bs, max_blocks, out_stride, 1, n_seqs, 1, scale * 1.4426950408889634f, qi};
+                    n_q, n_kv, bs, max_blocks, out_stride, 1, n_seqs, 1, scale * kLog2e, qi};
   int* done = flow + 64 * kFlowPad;
   int* err = flow + 128 * kFlowPad;
   const int G = n_q / n_kv;
