@@ -5,7 +5,8 @@ Registers model tools on the :class:`ToolRouter`:
 
 * ``llm.generate:<model>`` — ``parameters = {prompt | prompt_token_ids, max_tokens, temperature,
   top_p, top_k, min_p, seed, ignore_eos, stop, stop_token_ids, logprobs, repetition_penalty,
-  frequency_penalty, presence_penalty, logit_bias, return: "text"|"struct"}``
+  frequency_penalty, presence_penalty, logit_bias, guided_regex, guided_choice, guided_json,
+  return: "text"|"struct"}``
 * ``llm.chat:<model>``     — same with ``messages = [{role, content}, ...]``, and optionally
   OpenAI ``tools`` / ``tool_choice`` plus ``execute_tools`` / ``tool_secret_id`` /
   ``max_tool_rounds`` (service/tool_calls.py): the struct output then also carries
@@ -23,6 +24,9 @@ that does not ask for the struct still gets the plain string.
 ``logit_bias`` (a Struct ``{"<token id>": -100..100}``, at most 300 entries) change what is sampled
 (ops/penalties.py); logprobs still describe the raw logits.  Unlike logprobs they may be combined
 with function tools.  A value out of range is ``INVALID_ARGUMENT``.
+``guided_regex`` (string), ``guided_choice`` (list of strings) and ``guided_json`` (a JSON Schema
+as a Struct, or as JSON text, which keeps integers exact) constrain the completion
+(engine/grammar.py); an unsupported pattern or schema keyword is ``INVALID_ARGUMENT``.
 """
 from __future__ import annotations
 
@@ -125,9 +129,12 @@ class LLMTool:
             rounds = tool_rounds(params.get("max_tool_rounds"))
         except ValueError as e:
             raise ToolError("INVALID_ARGUMENT", str(e))
-        oc = await run_chat(self.llm, self.tok.chat_template, msgs, sp, tc[0], tc[1], router=self.router,
-                            execute=bool(params.get("execute_tools")), secret_id=params.get("tool_secret_id"),
-                            max_rounds=rounds, request_id=ctx.request_id)
+        try:
+            oc = await run_chat(self.llm, self.tok.chat_template, msgs, sp, tc[0], tc[1], router=self.router,
+                                execute=bool(params.get("execute_tools")), secret_id=params.get("tool_secret_id"),
+                                max_rounds=rounds, request_id=ctx.request_id)
+        except ValueError as e:  # a strict tool's schema the grammar compiler does not support
+            raise ToolError("INVALID_ARGUMENT", str(e))
         resp = proto.ExecuteToolResponse(status=_status())
         if params.get("return") == "struct" or oc.tool_calls or oc.executed:
             m = oc.metrics or {}

@@ -24,6 +24,13 @@ Penalties: ``frequency_penalty`` / ``presence_penalty`` (-2..2), ``repetition_pe
 ``logit_bias`` ({token id: -100..100}, at most 300 entries) are applied before sampling
 (ops/penalties.py); out-of-range values are a 400.  They may be combined with function tools, and
 logprobs keep describing the raw logits.
+
+Guided decoding: ``guided_regex``, ``guided_choice`` and ``guided_json`` (extensions, both
+endpoints) and ``response_format: {"type": "json_schema", "json_schema": {"schema": ...}}`` (mapped
+to ``guided_json``) constrain the completion on the GPU (engine/grammar.py, ops/grammar.py); an
+unsupported pattern or schema keyword is a 400 carrying the compiler's message.
+``response_format: {"type": "json_object"}`` is ignored.  A completion cut by ``max_tokens``
+(``finish_reason: "length"``) may be a prefix of a match.
 """
 
 
@@ -40,7 +47,7 @@ from ..service.tool_calls import run_chat, tool_rounds, validate_tools
 
 _SAMPLING_KEYS = ("max_tokens", "temperature", "top_p", "top_k", "min_p", "seed", "stop", "ignore_eos",
                   "stop_token_ids", "cache_salt", "repetition_penalty", "frequency_penalty", "presence_penalty",
-                  "logit_bias")
+                  "logit_bias", "guided_regex", "guided_choice", "guided_json")
 
 
 
@@ -64,6 +71,17 @@ def _llm(router, model: Optional[str]):
 def _params(body: Dict[str, Any], chat: bool = True) -> SamplingParams:
     d = {k: body[k] for k in _SAMPLING_KEYS if k in body and body[k] is not None}
     d["logprobs"] = lpf.parse_openai(body, chat)
+    if "guided_choice" in d and not d["guided_choice"]:
+        raise ValueError("guided_choice must be a non-empty list of non-empty strings")
+    rf = body.get("response_format")
+    if isinstance(rf, dict) and rf.get("type") == "json_schema":  # (json_object and text: ignored)
+        js = rf.get("json_schema")
+        if not isinstance(js, dict) or not isinstance(js.get("schema"), (dict, str)):
+            raise ValueError("response_format json_schema needs 'json_schema': {'schema': {...}}")
+        if any(k in d for k in ("guided_regex", "guided_choice", "guided_json")):
+            raise ValueError("at most one of response_format json_schema, guided_regex, guided_choice and "
+                             "guided_json may be set")
+        d["guided_json"] = js["schema"]
     if "max_completion_tokens" in body and "max_tokens" not in d:
         d["max_tokens"] = body["max_completion_tokens"]
     d.setdefault("max_tokens", 256)

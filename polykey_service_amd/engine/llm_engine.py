@@ -21,6 +21,7 @@ from ..models import build_model
 from ..models.config import ModelConfig, get_config
 from ..ops.sampler import logprob_entry
 from ..parallel.state import ParallelState, get_state
+from . import grammar
 from .model_runner import ModelRunner, RunnerConfig
 from .scheduler import ScheduledBatch, Scheduler
 from .sequence import FinishReason, RequestOutput, SamplingParams, Sequence, seq_metrics
@@ -136,6 +137,10 @@ class LLMEngine:
                             hip_graphs=cfg.hip_graphs, graph_batch_sizes=tuple(cfg.graph_batch_sizes),
                             kv_cache_dtype=cfg.kv_cache_dtype)
         self.runner = ModelRunner(model, rcfg, dev)
+        # guided decoding: the byte string of every vocabulary id, built once and kept on the device
+        off, data = grammar.token_bytes(self.tokenizer, mcfg.vocab_size)
+        self._single_bytes = grammar.single_byte_tokens(off, data)
+        self.runner.init_grammar(off, data)
         self._serving_preflight(mcfg)
         nblocks = self.runner.allocate_kv_cache()
         self.kv_bytes_per_token = self.runner.kv_bytes_per_block() // cfg.block_size
@@ -147,6 +152,10 @@ class LLMEngine:
         self.runner.bm = self.bm
         self.scheduler = Scheduler(self.bm, cfg.max_num_seqs, cfg.max_num_batched_tokens, cfg.max_model_len,
                                    policy=cfg.sched_policy, max_decode_stall=cfg.max_decode_stall)
+        # (the runner's own method and the scheduler's registry, not a method of this engine: a
+        # reference back to the engine would be a cycle, and an engine that only the cyclic
+        # collector can free may be torn down in the middle of a later engine's graph capture)
+        self.runner.live_requests = self.scheduler.by_request
         self.scheduler.on_free = self.runner.release_penalty_slot
         if cfg.hip_graphs and dev.type == "cuda":
             self.runner.capture_graphs()
@@ -187,9 +196,33 @@ class LLMEngine:
             raise ValueError("prompt token id out of range")
         if any(not 0 <= t < self.mcfg.vocab_size for t, _ in params.logit_bias):
             raise ValueError("logit_bias token id out of range")
+        g = self._grammar(params)
         seq = Sequence(request_id or uuid.uuid4().hex, prompt_ids, params, self.mcfg.eos_token_id, user)
-        self.scheduler.add(seq)
+        if g is None:
+            self.scheduler.add(seq)
+            return seq
+        seq.grammar = g
+        self.runner.acquire_grammar(seq)
+        try:
+            self.scheduler.add(seq)
+        except Exception:
+            self.runner.release_grammar(seq)
+            raise
         return seq
+
+    def _grammar(self, params: SamplingParams):
+        """The compiled constraint of a guided request (from the LRU), checked against this
+        engine's vocabulary; ValueError for what cannot be served."""
+        if not params.guided:
+            return None
+        V = self.mcfg.vocab_size
+        if not 0 <= self.mcfg.eos_token_id < V:
+            raise ValueError("guided decoding needs a model with an eos_token_id")
+        if any(not 0 <= t < V for t in params.stop_token_ids):
+            raise ValueError("stop_token_ids out of range")
+        g = grammar.grammar_for(params)
+        grammar.check_vocab(g, self._single_bytes)
+        return g
 
     def abort(self, request_id: str) -> Optional[Sequence]:
         return self.scheduler.abort(request_id)

@@ -36,6 +36,7 @@ import torch
 from ..ops import attention as attn_ops
 from ..ops import gemm
 from ..ops import native
+from ..ops import grammar as gram_ops
 from ..ops import penalties as pen_ops
 from ..ops import sampler as sampler_ops
 from .scheduler import ScheduledBatch
@@ -141,6 +142,20 @@ class ModelRunner:
         self._pen_slot: Dict[int, int] = {}                       # seq_id -> slot
         self._pen_free: List[int] = list(range(cfg.max_num_seqs - 1, -1, -1))
         self._pen_stale: set = set()                              # seq ids to re-seed from host truth
+        # guided decoding (ops/grammar.py): a byte DFA per constrained sequence, masked into the
+        # penalty slot's fp32 row and advanced on the device.  A guided sequence takes a penalty
+        # slot even with neutral penalties; its table and its slot record are (re-)seeded at the
+        # same points as the token history.  Tables are shared by grammar hash and refcounted by
+        # live sequences; an unreferenced one stays until its pool entry is needed.
+        self.gram: Optional[gram_ops.GrammarState] = None         # init_grammar
+        self._gram_key: List[Optional[str]] = [None] * gram_ops.N_TABLES  # pool entry -> grammar hash
+        self._gram_ref: List[int] = [0] * gram_ops.N_TABLES
+        self._gram_used: List[int] = [0] * gram_ops.N_TABLES      # last-use tick per entry (eviction order)
+        self._gram_tick = 0
+        self._gram_loaded: set = set()                            # entries whose words are on the device
+        self._gram_seq: Dict[int, int] = {}                       # seq_id -> the entry it references
+        self._gram_slots: set = set()                             # slots whose device record names a table
+        self.live_requests: Optional[dict] = None                 # Scheduler.by_request (LLMEngine)
         self.kv_caches: List[Tuple[torch.Tensor, torch.Tensor]] = []
         self.num_blocks = 0
         self.graphs: Dict[int, torch.cuda.CUDAGraph] = {}
@@ -293,11 +308,117 @@ class ModelRunner:
         h["pres"][r] = p.presence_penalty
 
     def release_penalty_slot(self, seq: Sequence) -> None:
-        """Scheduler.on_free: the sequence's blocks were freed (finish, abort, preemption)."""
+        """Scheduler.on_free: the sequence's blocks were freed (finish, abort, preemption).  A
+        sequence that will not run again (finished, or aborted: no longer in the scheduler's
+        registry ``live_requests``) drops its reference to a grammar table too; a preempted one
+        keeps it for its readmission."""
         slot = self._pen_slot.pop(seq.seq_id, None)
         self._pen_stale.discard(seq.seq_id)
         if slot is not None:
             self._pen_free.append(slot)
+        live = self.live_requests
+        if seq.is_finished() or (live is not None and live.get(seq.request_id) is not seq):
+            self.release_grammar(seq)
+
+    # ------------------------------------------------------------------ guided decoding
+    def init_grammar(self, off: np.ndarray, data: np.ndarray) -> None:
+        """The vocabulary's byte table (engine/grammar.py token_bytes), once, before the KV cache is
+        sized and before graphs are captured: from here on every sampling step masks and advances."""
+        self.gram = gram_ops.GrammarState(self.cfg.max_num_seqs, off, data, self.device)
+
+    def acquire_grammar(self, seq: Sequence) -> None:
+        """LLMEngine.add_request: ``seq.grammar`` gets a pool entry (shared by hash) and holds a
+        reference to it until the sequence ends."""
+        key = seq.grammar.key
+        n = gram_ops.N_TABLES
+        entry = next((i for i in range(n) if self._gram_key[i] == key), None)
+        if entry is None:
+            idle = [i for i in range(n) if self._gram_ref[i] == 0]
+            if not idle:
+                raise ValueError(f"all {n} grammar tables are held by live sequences: at most {n} distinct "
+                                 "guided_regex / guided_choice / guided_json constraints can be live at once")
+            entry = min(idle, key=lambda i: (self._gram_key[i] is not None, self._gram_used[i]))
+            self._gram_key[entry] = key
+            self._gram_loaded.discard(entry)
+        self._gram_ref[entry] += 1
+        self._gram_tick += 1
+        self._gram_used[entry] = self._gram_tick
+        self._gram_seq[seq.seq_id] = entry
+
+    def release_grammar(self, seq: Sequence) -> None:
+        entry = self._gram_seq.pop(seq.seq_id, None)
+        if entry is not None:
+            self._gram_ref[entry] -= 1
+
+    def grammar_end_ids(self, seq: Sequence) -> List[int]:
+        """The ids on which ``Sequence.append_token`` returns STOP: eos plus the stop_token_ids."""
+        return list(dict.fromkeys([seq.eos_token_id, *seq.params.stop_token_ids]))[:gram_ops.MAX_END]
+
+    def grammar_host_state(self, seq: Sequence) -> int:
+        """Host truth of a sequence's automaton state: the walk of ``output_ids`` from state 0."""
+        g, ends = seq.grammar, set(self.grammar_end_ids(seq))
+        off, data = self.gram.off_np, self.gram.data_np
+        state = 0
+        for t in seq.output_ids:
+            if t not in ends and 0 <= t < self.gram.vocab:
+                state = g.walk(state, data[off[t]:off[t + 1]].tobytes())
+        return state
+
+    def _seed_grammar(self, todo: List[Sequence]) -> None:
+        """After the token histories of ``todo`` were seeded (_seed_penalties): tables that are not
+        on the device yet are loaded, in chunks of one message each, then every sequence's slot
+        record is written: (table entry, host-truth state, end ids) for a guided one, "no table"
+        for a slot whose previous owner was guided.  Both travel as messages of their own through
+        the staging buffer, so TP workers run the same kernels on the same bytes."""
+        if self.gram is None:
+            return
+        cap = self.layout.max_tokens
+        entries: List[int] = []
+        for s in todo:
+            slot = self._pen_slot[s.seq_id]
+            if s.grammar is None:
+                if slot in self._gram_slots:
+                    self._gram_slots.discard(slot)
+                    entries += [slot, -1, -1, 0] + [-1] * gram_ops.MAX_END
+                continue
+            entry = self._gram_seq[s.seq_id]
+            if entry not in self._gram_loaded:
+                words = gram_ops.pack(s.grammar.cmap, s.grammar.trans, s.grammar.accept)
+                for w0 in range(0, words.size, cap):
+                    self._send_grammar(self.MODE_GLOAD, words[w0:w0 + cap], entry, w0)
+                self._gram_loaded.add(entry)
+            ends = self.grammar_end_ids(s)
+            self._gram_slots.add(slot)
+            entries += [slot, entry, self.grammar_host_state(s), len(ends)] + ends + [-1] * (gram_ops.MAX_END - len(ends))
+        per_msg = max(1, cap // gram_ops.SEED_WORDS) * gram_ops.SEED_WORDS
+        for e0 in range(0, len(entries), per_msg):
+            chunk = entries[e0:e0 + per_msg]
+            self._send_grammar(self.MODE_GSEED, np.asarray(chunk, dtype=np.int32), len(chunk) // gram_ops.SEED_WORDS, 0)
+
+    def _send_grammar(self, mode: int, words: np.ndarray, a: int, b: int) -> None:
+        self._next_staging()
+        h = self.h
+        h["input_ids"][:words.size] = words
+        h["header"][:9] = (mode, words.size, a, b, 0, 0, 0, 0, 0)
+        off, _ = self.layout.sections["input_ids"]
+        self._publish_words((off + words.size + 3) // 4 * 4)
+        self._run_grammar(mode, words.size, a, b)
+
+    def _run_grammar(self, mode: int, n_words: int, a: int, b: int) -> None:
+        """MODE_GLOAD: ``n_words`` of table entry ``a`` from word ``b``; MODE_GSEED: ``a`` slot records."""
+        if mode == self.MODE_GLOAD:
+            gram_ops.load(self.gram, a, b, self.d["input_ids"], n_words)
+        else:
+            gram_ops.seed(self.gram, self.d["input_ids"], a)
+        self.stats["grammar_msgs"] = self.stats.get("grammar_msgs", 0) + 1
+
+    def grammar_state(self, seq: Sequence):
+        """Audit read-back (tests): the device's (table entry, state) of ``seq``; None when the
+        sequence holds no slot or no grammar."""
+        slot = self._pen_slot.get(seq.seq_id)
+        if slot is None or seq.grammar is None or self.gram is None:
+            return None
+        return gram_ops.read_slot(self.gram, slot)
 
     def _seed_penalties(self, sampling: List[Sequence]) -> None:
         """Before a step is packed: every penalised sampling sequence without a slot (first
@@ -308,10 +429,14 @@ class ModelRunner:
         id stream in ``input_ids``, the entry table in ``positions``.  A message holds at most
         one entry per slot (entries of one launch run concurrently); a history that does not
         fit continues in the next message with clear = 0."""
-        todo = [s for s in sampling if s.params.has_penalties
+        todo = [s for s in sampling if (s.params.has_penalties or s.grammar is not None)
                 and (s.seq_id not in self._pen_slot or s.seq_id in self._pen_stale)]
         if not todo:
             return
+        self._seed_history(todo)
+        self._seed_grammar(todo)
+
+    def _seed_history(self, todo: List[Sequence]) -> None:
         cap = self.layout.max_tokens
         max_entries = max(1, cap // pen_ops.ENTRY_WORDS)
         ids: List[int] = []
@@ -390,7 +515,9 @@ class ModelRunner:
     # header words (section "header"): mode, T, n, nd, ns, max_q, graph bucket, short-context graph,
     # continuation (input ids = the previous step's sampled ids, already on the device)
     # MODE_SEED: header = (mode, id words, entries); seeds penalty slots (_seed_penalties)
-    MODE_IDLE, MODE_RUN, MODE_STOP, MODE_SEED = 0, 1, 2, 3
+    # MODE_GLOAD: header = (mode, words, table entry, first word); MODE_GSEED: (mode, words, slot
+    # records): guided decoding tables and slot records (_seed_grammar), payload in "input_ids"
+    MODE_IDLE, MODE_RUN, MODE_STOP, MODE_SEED, MODE_GLOAD, MODE_GSEED = 0, 1, 2, 3, 4, 5
 
     @torch.inference_mode()
     def execute(self, batch: ScheduledBatch) -> List[int]:
@@ -626,6 +753,11 @@ class ModelRunner:
                 with torch.inference_mode():
                     self._run_seed(T, n)
                 continue
+            if mode in (self.MODE_GLOAD, self.MODE_GSEED):
+                self._stage_local(nbytes // 4)
+                with torch.inference_mode():
+                    self._run_grammar(mode, T, n, nd)
+                continue
             if mode != self.MODE_RUN:
                 continue
             self._stage_local(nbytes // 4)
@@ -713,15 +845,21 @@ class ModelRunner:
         return self._sample(logits, ns)
 
     def _sample(self, logits: torch.Tensor, ns: int) -> torch.Tensor:
-        """logits → penalised copy of the rows with a slot → sample (those rows from the copy) →
-        logprobs (from the raw logits) → count the sampled ids.  Eager and inside every graph."""
+        """logits → penalised copy of the rows with a slot → grammar mask on that copy → sample (those
+        rows from the copy) → logprobs (from the raw logits) → count the sampled ids → advance the
+        grammar states.  Eager and inside every graph."""
         d = self.d
+        V = logits.shape[-1]
         pen_out = pen_ops.apply(self.pen, logits, d["pen_slot"], d["rep"], d["freq"], d["pres"])
+        if self.gram is not None:
+            gram_ops.mask(self.gram, pen_out, d["pen_slot"], ns, V)
         toks = sampler_ops.sample(logits, d["temperature"][:ns], d["top_k"][:ns], d["top_p"][:ns],
                                   d["min_p"][:ns], d["seeds"][:ns], d["offsets"][:ns],
                                   alt=pen_out, alt_slots=d["pen_slot"])
         sampler_ops.logprobs(logits, toks, d["logprobs"][:ns], self.lp_dev)
         pen_ops.update(self.pen, d["pen_slot"], toks, ns)
+        if self.gram is not None:
+            gram_ops.advance(self.gram, d["pen_slot"], toks, ns, V)
         return toks
 
     # ------------------------------------------------------------------ graphs

@@ -4,12 +4,14 @@ from __future__ import annotations
 import dataclasses
 import enum
 import itertools
+import json
 import math
 import time
 from typing import List, Optional, Sequence as Seq
 
 
 MAX_LOGPROBS = 20  # longest top_logprobs list (the logprobs kernel's compile-time constant)
+MAX_GUIDED_STOP_IDS = 16  # plus eos: the 17 end ids of a grammar slot (ops/grammar.py)
 MAX_LOGIT_BIAS = 300  # longest logit_bias list (the penalty kernels' per-slot table, ops/penalties.py)
 
 
@@ -50,11 +52,21 @@ class SamplingParams:
     frequency_penalty: float = 0.0
     presence_penalty: float = 0.0
     logit_bias: Seq = ()          # sorted tuple of (token id, bias) pairs (from_dict also takes a dict)
+    # guided decoding (engine/grammar.py): at most one of a regex the completion must full-match, a
+    # list of strings it must be one of, or a JSON Schema (canonical JSON text) it must conform to
+    guided_regex: Optional[str] = None
+    guided_choice: Seq[str] = ()
+    guided_json: Optional[str] = None
+    guided_suffix: str = ""       # literal text after the guided_json value (a forced tool call's closing)
 
     @property
     def has_penalties(self) -> bool:
         return (self.repetition_penalty != 1.0 or self.frequency_penalty != 0.0 or self.presence_penalty != 0.0
                 or len(self.logit_bias) > 0)
+
+    @property
+    def guided(self) -> bool:
+        return self.guided_regex is not None or len(self.guided_choice) > 0 or self.guided_json is not None
 
     def validate(self, max_model_len: int) -> None:
         if self.max_tokens < 1:
@@ -88,6 +100,28 @@ class SamplingParams:
             if any(not math.isfinite(b) or not -100 <= b <= 100 for _, b in lb):
                 raise ValueError("logit_bias values must be in [-100, 100]")
             self.logit_bias = lb
+        if self.guided_regex is not None and not isinstance(self.guided_regex, str):
+            raise ValueError("guided_regex must be a string")
+        gc = self.guided_choice
+        if isinstance(gc, (str, bytes)) or not isinstance(gc, (list, tuple)) or any(
+                not isinstance(c, str) or not c for c in gc):
+            raise ValueError("guided_choice must be a non-empty list of non-empty strings")
+        self.guided_choice = tuple(gc)
+        if isinstance(self.guided_json, dict):
+            self.guided_json = json.dumps(self.guided_json, sort_keys=True)
+        if self.guided_json is not None and not isinstance(self.guided_json, str):
+            raise ValueError("guided_json must be a JSON Schema (a dict, or its JSON text)")
+        if not isinstance(self.guided_suffix, str) or (self.guided_suffix and self.guided_json is None):
+            raise ValueError("guided_suffix needs guided_json")
+        if (self.guided_regex is not None) + bool(gc) + (self.guided_json is not None) > 1:
+            raise ValueError("at most one of guided_regex, guided_choice and guided_json may be set")
+        if self.guided:
+            if self.ignore_eos:
+                raise ValueError("guided decoding cannot be combined with ignore_eos")
+            if len(self.stop_token_ids) > MAX_GUIDED_STOP_IDS:
+                raise ValueError(f"a guided request takes at most {MAX_GUIDED_STOP_IDS} stop_token_ids")
+            from . import grammar  # compiled here (and cached) so that every front end rejects it early
+            grammar.grammar_for(self)
 
     @classmethod
     def from_dict(cls, d: dict) -> "SamplingParams":
@@ -114,6 +148,26 @@ class SamplingParams:
                 elif f.name == "ignore_eos":
                     v = bool(v)
                 elif f.name == "cache_salt":
+                    v = str(v)
+                elif f.name == "guided_regex":
+                    if not isinstance(v, str):
+                        raise ValueError("guided_regex must be a string")
+                elif f.name == "guided_choice":
+                    # (an empty list is the unset field as it comes back over the remote-engine wire)
+                    if isinstance(v, (str, bytes)) or not isinstance(v, (list, tuple)) or any(
+                            not isinstance(c, str) or not c for c in v):
+                        raise ValueError("guided_choice must be a non-empty list of non-empty strings")
+                    v = tuple(v)
+                elif f.name == "guided_json":
+                    if isinstance(v, str):
+                        try:
+                            v = json.loads(v)
+                        except ValueError:
+                            raise ValueError("guided_json is not valid JSON") from None
+                    if not isinstance(v, dict):
+                        raise ValueError("guided_json must be a JSON Schema (a dict, or its JSON text)")
+                    v = json.dumps(v, sort_keys=True)
+                elif f.name == "guided_suffix":
                     v = str(v)
                 elif f.name == "logprobs":
                     if isinstance(v, bool) or (isinstance(v, float) and v != int(v)):
@@ -143,7 +197,7 @@ class Sequence:
     __slots__ = ("seq_id", "request_id", "prompt_ids", "output_ids", "params", "status", "num_computed",
                  "arrival", "first_scheduled", "first_token_time", "finish_time", "finish_reason",
                  "num_preemptions", "eos_token_id", "token_times", "user", "num_cached_tokens",
-                 "cache_salt", "logprobs")
+                 "cache_salt", "logprobs", "grammar")
 
     def __init__(self, request_id: str, prompt_ids: List[int], params: SamplingParams, eos_token_id: int = -1,
                  user=None, cache_salt: Optional[str] = None):
@@ -165,6 +219,7 @@ class Sequence:
         self.token_times: List[float] = []
         # one (logprob, [(id, logprob) x n]) per output token; None unless params.logprobs is set
         self.logprobs: Optional[list] = [] if getattr(params, "logprobs", None) is not None else None
+        self.grammar = None  # the request's compiled constraint (engine/grammar.py), set by add_request
         self.user = user
         # prefix-cache namespace (Scheduler._salt); None = the request's params.cache_salt
         self.cache_salt = cache_salt if cache_salt is not None else getattr(params, "cache_salt", None)

@@ -49,6 +49,10 @@ SIGNATURES = {
     "pk_penalty_seed": [P, I64, P, P, P, P, I32, P, I32, I32, I32, P],
     "pk_penalty_apply": [P, I64, P, I64, I32, I32, I32, P, I64, P, P, P, P, P, P, P, I32, P],
     "pk_penalty_update": [P, I64, P, P, I32, I32, I32, P],
+    "pk_grammar_load": [P, I32, I32, I32, P, I32, P],
+    "pk_grammar_seed": [P, I32, P, I32, P],
+    "pk_grammar_mask": [P, I64, I32, I32, P, I32, P, I32, P, P, P, I32, P],
+    "pk_grammar_advance": [P, I32, P, I32, P, P, I32, P, P, I32, I32, P],
     "pk_embedding": [P, P, P, I32, I32, I32, I32, P],
     "pk_moe_topk_softmax": [P, P, P, I32, I32, I32, I32, I32, P],
     "pk_moe_align": [P, P, P, P, I32, I32, I32, I32, P],

@@ -418,3 +418,151 @@ def penalty_update(counts, slots, tokens, V: int) -> None:
         slot, t = int(slots[r]), int(tokens[r])
         if 0 <= slot < c.shape[0] and 0 <= t < V and (c[slot, t] & 0x7FFF) != 0x7FFF:
             c[slot, t] += 1
+
+
+# --------------------------------------------------------------------------- guided decoding
+# The device state of ops/grammar.py.  A pool entry is GRAMMAR_TABLE_WORDS int32 words holding one
+# byte DFA (engine/grammar.py): [0] states S, [1] byte classes C, [2:4] zero, [4:68] the class of
+# every byte (256 x uint8), [68:132] one accept bit per state (bit s & 31 of word s >> 5), then
+# trans[S][C] as int16, two per word, little end first; -1 = DEAD.  An entry whose S or C is out
+# of range (a never-loaded one holds zeros) is no table.  A slot record is GRAMMAR_SLOT_WORDS
+# words: table entry (-1 = none), current state (-1 = DEAD), number of end ids, 17 end ids.
+GRAMMAR_MAX_STATES = 2048
+GRAMMAR_N_TABLES = 16
+GRAMMAR_MAX_END = 17
+GRAMMAR_HEAD_WORDS = 132
+GRAMMAR_TABLE_WORDS = GRAMMAR_HEAD_WORDS + GRAMMAR_MAX_STATES * 256 // 2
+GRAMMAR_SLOT_WORDS = 3 + GRAMMAR_MAX_END
+GRAMMAR_SEED_WORDS = 4 + GRAMMAR_MAX_END  # slot, table entry, state, number of end ids, 17 end ids
+
+
+def grammar_pack(cmap, trans, accept) -> np.ndarray:
+    """A DFA (``cmap`` uint8[256], ``trans`` int16[S, C], ``accept`` bool[S]) as the int32 words of
+    a pool entry, cut after the last transition."""
+    S, C = trans.shape
+    assert 1 <= S <= GRAMMAR_MAX_STATES and 1 <= C <= 256 and int(np.max(cmap)) < C
+    t = np.ascontiguousarray(trans, dtype="<i2").reshape(-1)
+    if t.size % 2:
+        t = np.concatenate([t, np.zeros(1, dtype="<i2")])
+    bits = np.zeros(GRAMMAR_MAX_STATES, dtype=np.uint8)
+    bits[:S] = np.asarray(accept, dtype=np.uint8)
+    acc = np.packbits(bits, bitorder="little").view("<u4").astype(np.uint32).view(np.int32)
+    head = np.array([S, C, 0, 0], dtype=np.int32)
+    return np.concatenate([head, np.asarray(cmap, dtype=np.uint8).view("<i4"), acc, t.view("<i4")]).astype(np.int32)
+
+
+def _grammar_table(words: np.ndarray):
+    """Pool entry words → (cmap, trans int16[S, C], accept bool[S]) or None for no table."""
+    S, C = int(words[0]), int(words[1])
+    if not (1 <= S <= GRAMMAR_MAX_STATES and 1 <= C <= 256):
+        return None
+    cmap = words[4:68].view(np.uint8)
+    acc = np.unpackbits(words[68:132].view(np.uint8), bitorder="little")[:S].astype(bool)
+    trans = words[GRAMMAR_HEAD_WORDS:GRAMMAR_HEAD_WORDS + (S * C + 1) // 2].view(np.int16)[:S * C].reshape(S, C)
+    return cmap, trans, acc
+
+
+def grammar_load(pool, entry: int, word_off: int, words) -> None:
+    """``pool[entry, word_off:word_off + len(words)] = words``; a chunk that does not fit is ignored."""
+    w = np.asarray(words, dtype=np.int32).reshape(-1)
+    if not 0 <= entry < pool.shape[0] or word_off < 0 or word_off + w.size > pool.shape[1]:
+        return
+    pool[entry, word_off:word_off + w.size] = torch.from_numpy(w.copy())
+
+
+def grammar_seed(rec, entries) -> None:
+    """Entries ``[n, 21]`` of (slot, table entry, state, number of end ids, 17 end ids) → slot records."""
+    for e in np.asarray(entries, dtype=np.int32).reshape(-1, GRAMMAR_SEED_WORDS):
+        if 0 <= int(e[0]) < rec.shape[0]:
+            rec[int(e[0])] = torch.from_numpy(e[1:].copy())
+
+
+def _grammar_row(pool, rec, slot: int):
+    """→ (table, state, end ids) of a slot, or None when it is out of range or holds no table."""
+    if not 0 <= slot < rec.shape[0]:
+        return None
+    r = rec[slot].numpy()
+    tab = int(r[0])
+    if not 0 <= tab < pool.shape[0]:
+        return None
+    table = _grammar_table(pool[tab].numpy())
+    if table is None:
+        return None
+    S = table[1].shape[0]
+    state = int(r[1]) if 0 <= int(r[1]) < S else -1
+    ends = r[3:3 + min(max(int(r[2]), 0), GRAMMAR_MAX_END)]
+    return table, state, ends
+
+
+def _grammar_walk_all(table, state: int, off: np.ndarray, data: np.ndarray, V: int, mutant=None) -> np.ndarray:
+    """The state every id ``< V`` leads to from ``state`` (-1 = DEAD), all ids at once."""
+    cmap, trans, _ = table
+    S, C = trans.shape
+    lens = np.diff(off[:V + 1]).astype(np.int64)
+    if mutant == "drop_last_byte":
+        lens = np.maximum(lens - 1, 0)
+    st = np.full(V, state, dtype=np.int64)
+    start = off[:V].astype(np.int64)
+    for j in range(int(lens.max()) if V else 0):
+        act = np.nonzero((lens > j) & (st >= 0))[0]
+        if act.size == 0:
+            break
+        cls = cmap[data[start[act] + j]].astype(np.int64)
+        nxt = trans[st[act], np.minimum(cls, C - 1)].astype(np.int64)
+        nxt[(cls >= C) | (nxt >= S)] = -1
+        st[act] = nxt
+    return st
+
+
+def grammar_mask(out, V: int, pool, rec, slots, B: int, off, data, mutant=None) -> None:
+    """In place on the fp32 rows ``out[slots[r]]`` of every ``r < B`` whose slot holds a table, for
+    every id ``t < V``: an end id is kept iff the state accepts (at DEAD end ids are kept); an id
+    with no bytes is dropped; any other id is kept iff walking its bytes from the current state
+    never hits DEAD.  Dropped = -inf, kept = untouched.  ``mutant`` names a deliberate defect
+    (tests/grammar_cases.py)."""
+    off = np.asarray(off)
+    data = np.asarray(data)
+    o = out.numpy()
+    for r in range(B):
+        slot = int(slots[r])
+        row = _grammar_row(pool, rec, slot)
+        if mutant == "next_table" and 0 <= slot < rec.shape[0] and int(rec[slot, 0]) >= 0:
+            t2 = _grammar_table(pool[(int(rec[slot, 0]) + 1) % pool.shape[0]].numpy())
+            row = None if t2 is None or row is None else (t2, row[1] if row[1] < t2[1].shape[0] else -1, row[2])
+        if row is None:
+            continue
+        table, state, ends = row
+        walk_from = 0 if mutant == "from_state_0" else state
+        fin = _grammar_walk_all(table, walk_from, off, data, V, mutant)
+        keep = fin >= 0
+        if mutant != "keep_empty":
+            keep &= np.diff(off[:V + 1]) > 0
+        end_ok = state < 0 or bool(table[2][state]) or mutant == "keep_end"
+        for t in ends:
+            if 0 <= int(t) < V:
+                keep[int(t)] = end_ok
+        o[slot, :V][~keep] = -np.inf
+
+
+def grammar_advance(pool, rec, slots, tokens, n: int, off, data, V: int, mutant=None) -> None:
+    """After sampling, per row with a table: an end id leaves the state alone, any other id ``< V``
+    moves it along the id's bytes (DEAD stays DEAD)."""
+    off = np.asarray(off)
+    data = np.asarray(data)
+    for r in range(n):
+        slot, t = int(slots[r]), int(tokens[r])
+        row = _grammar_row(pool, rec, slot)
+        if row is None or not 0 <= t < V:
+            continue
+        (cmap, trans, _), state, ends = row
+        if mutant != "advance_on_end" and t in [int(x) for x in ends]:
+            continue
+        S, C = trans.shape
+        for b in data[off[t]:off[t + 1]]:
+            if state < 0:
+                break
+            c = int(cmap[b])
+            state = int(trans[state, c]) if c < C else -1
+            if state >= S:
+                state = -1
+        rec[slot, 1] = state

@@ -18,7 +18,9 @@ itself names the tool:
 
 OpenAI semantics kept: ``arguments`` is a JSON string (the model's own text when it did not
 produce valid JSON, as OpenAI documents), ``finish_reason`` is ``"tool_calls"`` when calls
-are returned to the client.
+are returned to the client.  A forced call of a named function defined with ``"strict": true``
+is decoded under the function's ``parameters`` schema (:func:`strict_params`), so its
+``arguments`` are always valid JSON of that schema.
 """
 from __future__ import annotations
 
@@ -176,6 +178,25 @@ def validate_tools(tools: Any, tool_choice: Any) -> Tuple[Optional[List[Dict[str
     return (tools or None), tool_choice
 
 
+def strict_params(sp, tools, name: str, family: str):
+    """A forced call of a *named* function whose definition carries OpenAI's ``"strict": true``:
+    the completion is constrained (guided decoding, engine/grammar.py) to the function's
+    ``parameters`` schema followed by the call's own closing, so :func:`forced_call` always finds
+    valid JSON arguments.  Without ``strict`` the sampling parameters are returned unchanged.
+    ValueError for a schema the grammar compiler does not support."""
+    fn = next((t.get("function", t) for t in tools or [] if isinstance(t, dict)
+               and isinstance(t.get("function", t), dict) and t.get("function", t).get("name") == name), None)
+    if not fn or fn.get("strict") is not True:
+        return sp
+    schema = fn.get("parameters")
+    if not isinstance(schema, dict):
+        schema = {"type": "object", "properties": {}}
+    out = dataclasses.replace(sp, guided_regex=None, guided_choice=(), guided_json=json.dumps(schema, sort_keys=True),
+                              guided_suffix="}]" if family == MISTRAL else "}")
+    out.validate(1 << 30)  # compiles the grammar: an unsupported schema fails the request here
+    return out
+
+
 @dataclasses.dataclass
 class ChatOutcome:
     content: str
@@ -252,8 +273,11 @@ async def run_chat(llm, template: ChatTemplate, messages: List[Dict[str, Any]], 
             forced_name = choice["function"]["name"] if isinstance(choice, dict) else (
                 names[0] if len(names) == 1 else None)
             text += template.call_prefix(forced_name)
+        sp_round = sp
+        if forced and isinstance(choice, dict):
+            sp_round = strict_params(sp, tools, forced_name, template.family)
         prompt_ids = tok.encode(text)
-        toks, last = await llm.generate_all(prompt_ids, sp, request_id=f"{rid}-{rnd}" if rnd else rid)
+        toks, last = await llm.generate_all(prompt_ids, sp_round, request_id=f"{rid}-{rnd}" if rnd else rid)
         n_prompt += len(prompt_ids)
         n_out += len(toks)
         out = tok.decode(toks, keep_special=active)
