@@ -42,6 +42,7 @@ class ServerConfig:
     gpu_mem_fraction: float = 0.90
     num_kv_blocks: int = 0         # 0 → size from free HBM
     kv_cache_dtype: str = "auto"   # auto | bf16 | fp8 (alias fp8_e4m3): KV-cache element type
+    weight_dtype: str = "auto"     # auto | bf16 | fp8 (alias fp8_e4m3): projection weight element type
     hip_graphs: bool = True
     device: str = "cuda"
     seed: int = 0
@@ -77,6 +78,7 @@ _ENV = {
     "gpu_mem_fraction": "POLYKEY_GPU_MEM_FRACTION",
     "num_kv_blocks": "POLYKEY_NUM_KV_BLOCKS",
     "kv_cache_dtype": "POLYKEY_KV_CACHE_DTYPE",
+    "weight_dtype": "POLYKEY_WEIGHT_DTYPE",
     "hip_graphs": "POLYKEY_HIP_GRAPHS",
     "device": "POLYKEY_DEVICE",
     "seed": "POLYKEY_SEED",
@@ -98,6 +100,27 @@ def normalize_kv_cache_dtype(value: str) -> str:
     if v in ("fp8", "fp8_e4m3"):
         return "fp8"
     raise ValueError(f"kv_cache_dtype must be one of {', '.join(KV_CACHE_DTYPES)} (got {value!r})")
+
+
+WEIGHT_DTYPES = ("auto", "bf16", "fp8")
+
+
+def normalize_weight_dtype(value: str) -> str:
+    """``--weight-dtype`` / ``POLYKEY_WEIGHT_DTYPE`` -> "bf16" or "fp8".  "auto" means bf16 and
+    "fp8_e4m3" is an alias of "fp8" (weight-only OCP e4m3, one scale per output channel); anything
+    else is an error."""
+    v = str(value).strip().lower()
+    if v in ("auto", "bf16"):
+        return "bf16"
+    if v in ("fp8", "fp8_e4m3"):
+        return "fp8"
+    raise ValueError(f"weight_dtype must be one of {', '.join(WEIGHT_DTYPES)} (got {value!r})")
+
+
+def env_weight_dtype(environ: Optional[Mapping[str, str]] = None) -> str:
+    """The weight dtype a config built without the field takes: ``POLYKEY_WEIGHT_DTYPE`` (the
+    variable of :data:`_ENV`), else "auto".  Explicit values always win."""
+    return (os.environ if environ is None else environ).get(_ENV["weight_dtype"], "") or "auto"
 
 
 def _flag_name(field: str) -> str:
@@ -141,4 +164,5 @@ def load_server_config(argv: Optional[Sequence[str]] = None,
             continue
         setattr(cfg, fname, val)
     cfg.kv_cache_dtype = normalize_kv_cache_dtype(cfg.kv_cache_dtype)
+    cfg.weight_dtype = normalize_weight_dtype(cfg.weight_dtype)
     return cfg

@@ -16,7 +16,7 @@ from typing import Callable, Dict, Iterable, List, Optional
 import torch
 
 from .._native.loader import load_extension
-from ..config.server_config import normalize_kv_cache_dtype
+from ..config.server_config import env_weight_dtype, normalize_kv_cache_dtype, normalize_weight_dtype
 from ..models import build_model
 from ..models.config import ModelConfig, get_config
 from ..ops.sampler import logprob_entry
@@ -45,6 +45,12 @@ class EngineConfig:
     # KV-cache element type: "auto" | "bf16" | "fp8" ("fp8_e4m3"): OCP e4m3 bytes with per-layer
     # k_scale / v_scale, half the bytes per token (README "KV cache dtype")
     kv_cache_dtype: str = "auto"
+    # projection weight element type: "auto" | "bf16" | "fp8" ("fp8_e4m3"): weight-only OCP e4m3 with
+    # one fp32 scale per output channel, quantised at set-up (README "Weight dtype").  Opt-in; a
+    # config built without it takes POLYKEY_WEIGHT_DTYPE (config/server_config.py env_weight_dtype),
+    # so with that variable set to fp8 every engine of the process asks for FP8 weights, and one
+    # that cannot have them (MoE, TP, EP) raises instead of quietly serving bf16
+    weight_dtype: str = dataclasses.field(default_factory=env_weight_dtype)
     graph_batch_sizes: tuple = ()
     watermark: float = 0.01
     device: str = ""
@@ -66,7 +72,8 @@ class EngineConfig:
                    block_size=sc.kv_block_size, max_num_seqs=sc.max_num_seqs,
                    max_num_batched_tokens=sc.max_num_batched_tokens, max_model_len=sc.max_model_len,
                    num_kv_blocks=sc.num_kv_blocks, gpu_mem_fraction=sc.gpu_mem_fraction, hip_graphs=sc.hip_graphs,
-                   num_layers=getattr(sc, "num_layers", 0), kv_cache_dtype=getattr(sc, "kv_cache_dtype", "auto"))
+                   num_layers=getattr(sc, "num_layers", 0), kv_cache_dtype=getattr(sc, "kv_cache_dtype", "auto"),
+                   weight_dtype=getattr(sc, "weight_dtype", "auto"))
 
 
 def tokenizer_for(cfg: EngineConfig, mcfg: Optional[ModelConfig] = None):
@@ -80,10 +87,20 @@ def tokenizer_for(cfg: EngineConfig, mcfg: Optional[ModelConfig] = None):
 
 class LLMEngine:
     def __init__(self, cfg: EngineConfig, st: Optional[ParallelState] = None, model=None):
-        cfg = dataclasses.replace(cfg, kv_cache_dtype=normalize_kv_cache_dtype(cfg.kv_cache_dtype))
+        cfg = dataclasses.replace(cfg, kv_cache_dtype=normalize_kv_cache_dtype(cfg.kv_cache_dtype),
+                                  weight_dtype=normalize_weight_dtype(cfg.weight_dtype))
         self.cfg = cfg
         self.st = st or get_state()
         mcfg: ModelConfig = get_config(cfg.model_path or cfg.model)
+        if cfg.weight_dtype == "fp8":
+            # weight-only FP8 covers the dense Llama projections on one GPU; no silent fallback
+            if mcfg.is_moe:
+                raise ValueError(f"weight_dtype=fp8 does not support MoE models ({mcfg.name}): the grouped "
+                                 "expert GEMMs are bf16-only")
+            if self.st.tp_size > 1:
+                raise ValueError(f"weight_dtype=fp8 does not support tp={self.st.tp_size}: FP8 weights are not sharded")
+            if self.st.ep_size > 1:
+                raise ValueError(f"weight_dtype=fp8 does not support ep={self.st.ep_size}: FP8 weights are not sharded")
         if cfg.num_layers > 0 and cfg.num_layers != mcfg.num_layers:
             mcfg = dataclasses.replace(mcfg, num_layers=cfg.num_layers)
         if cfg.max_model_len > mcfg.max_position:
@@ -128,8 +145,19 @@ class LLMEngine:
             else:
                 model.init_random(cfg.seed)
         self.model = model
+        if cfg.weight_dtype == "fp8":
+            if not hasattr(model, "weight_dtype"):
+                raise ValueError(f"weight_dtype=fp8 is not supported by {type(model).__name__}")
+            model.weight_dtype = "fp8"  # before pack_decode_weights, which quantises
+        elif getattr(model, "w8", False):
+            raise ValueError(f"weight_dtype={cfg.weight_dtype} with a model whose projections are already FP8: "
+                             "pass weight_dtype=fp8")
         if hasattr(model, "pack_decode_weights"):
             model.pack_decode_weights()
+        self.weight_bytes = model.projection_bytes() if hasattr(model, "projection_bytes") else 0
+        if cfg.weight_dtype != "fp8":
+            logging.getLogger(__name__).info("weights: dtype %s, %d projection bytes, 0 widen-scratch bytes",
+                                             cfg.weight_dtype, self.weight_bytes)
         self.tokenizer = tokenizer_for(cfg, mcfg)
         rcfg = RunnerConfig(block_size=cfg.block_size, max_num_seqs=cfg.max_num_seqs,
                             max_num_batched_tokens=cfg.max_num_batched_tokens, max_model_len=cfg.max_model_len,

@@ -24,6 +24,10 @@ QKV / gate_up weights and every projection is the hand-written weight-streaming 
     mlp_fused        gate_up + SiLU handed in-launch to the down projection's slabs
                   -> residual update + norm parts (TP: the fused collective)
 
+With ``weight_dtype = "fp8"`` (TP = 1) the four projections are weight-only FP8 handles
+(ops/gemm_w8.py): the same chain in its two-launch forms on the W8 decode GEMM (gemm_w8.hip), the
+general path on the same kernel up to 512 rows and on widen -> library GEMM -> column scale above.
+
 Vocab-parallel embedding and LM head for TP>1 (logits all-gathered for sampling).
 """
 from __future__ import annotations
@@ -41,6 +45,7 @@ from .. import ops
 from ..ops import attention as attn_ops
 from ..ops import gemm
 from ..ops import gemm_prefill
+from ..ops import gemm_w8
 from ..ops import moe as moe_ops
 from ..ops import reference
 from ..parallel import comm
@@ -131,6 +136,19 @@ def pack_folded(owner, name: str, norm_w: torch.Tensor, packed_only: bool) -> to
     return out
 
 
+def _proj_out_w8(x: torch.Tensor, w: gemm_w8.W8, ws: Optional[torch.Tensor], half: bool = False):
+    """:func:`_proj_out` on FP8 weights (TP = 1): decode-sized M returns the split-K slabs
+    unreduced, anything else bf16 (the W8 kernel, or its wide path above its row limit)."""
+    M, N = x.shape[0], w.shape[0]
+    if ws is not None and gemm_w8.kernel_ok(x, gemm.SKINNY_MAX_M) and gemm.norm_fusable(N):
+        S, _ = gemm.partial_tiling(N, x.shape[1], M, w.packed, half)
+        if ws.numel() >= S * M * N:
+            return gemm_w8.linear_partial(x, w, ws, half=half)
+    # unsplit, o / down have too few n-blocks for the chip: above 64 rows the wide path is the
+    # faster one (8B down at 256 rows: 84 vs 145 us, profiles/w8_gemm.md), as hipBLASLt is for bf16
+    return gemm_w8.linear(x, w, max_m=gemm.SKINNY_MAX_M)
+
+
 def add_norm(pending, residual: torch.Tensor, w: torch.Tensor, eps: float):
     """residual += pending; x = rms_norm(residual) * w → (x, residual)."""
     if isinstance(pending, gemm.Partial):
@@ -169,6 +187,8 @@ class LlamaAttention(nn.Module):
         split-K :class:`~polykey_service_amd.ops.gemm.Partial` consumed by the next norm."""
         T = x.shape[0]
         k_cache, v_cache = kv
+        if isinstance(self.qkv_p, gemm_w8.W8):
+            return self._forward_w8(x, positions, md, cos_sin, kv, ws)
         S = gemm.choose_split(self.qkv.shape[0], x.shape[1], T)
         # (a cache without the split-K epilogue writer: its steps with prefill take linear -> rope_and_cache)
         if (ws is not None and gemm.skinny_ok(x, self.qkv) and S > 1 and ws.numel() >= S * T * self.qkv.shape[0]
@@ -188,6 +208,29 @@ class LlamaAttention(nn.Module):
                                                    cos_sin, kv)), self.o, ws, self.o_p)
         a = attn_ops.paged_attention(q, k_cache, v_cache, md, self.scale, k_scale=self.k_scale, v_scale=self.v_scale)
         return _proj_out(self.drop(a), self.o, ws, self.o_p, half=True)
+
+    def _forward_w8(self, x: torch.Tensor, positions: torch.Tensor, md: attn_ops.AttnMetadata, cos_sin: torch.Tensor,
+                    kv: Tuple[torch.Tensor, torch.Tensor], ws: Optional[torch.Tensor]):
+        """:meth:`forward` on FP8 weights (``qkv_p`` / ``o_p`` are :class:`gemm_w8.W8` handles with
+        ln1 folded into QKV; ``x`` is normalised with unit weights): the same launches, W8 GEMMs."""
+        T = x.shape[0]
+        k_cache, v_cache = kv
+        N = self.qkv_p.shape[0]
+        S = gemm.choose_split(N, x.shape[1], T)
+        if (ws is not None and gemm_w8.kernel_ok(x, gemm.SKINNY_MAX_M) and S > 1 and ws.numel() >= S * T * N
+                and (md.num_prefill == 0 or attn_ops.slab_writers_ok(k_cache))):
+            p = gemm_w8.linear_partial(x, self.qkv_p, ws, S)
+            if md.num_prefill == 0:
+                a = attn_ops.paged_decode_from_qkv(p, positions, cos_sin, k_cache, v_cache, md, self.scale,
+                                                   self.nq, self.nkv, k_scale=self.k_scale, v_scale=self.v_scale)
+            else:
+                q = gemm.qkv_reduce_rope_cache(p, positions, cos_sin, k_cache, v_cache, md.slot_mapping, self.nq,
+                                               self.nkv)
+                a = attn_ops.paged_attention(q, k_cache, v_cache, md, self.scale, k_scale=self.k_scale,
+                                             v_scale=self.v_scale)
+            return _proj_out_w8(self.drop(a), self.o_p, ws, half=True)
+        a = self.attend(gemm_w8.linear(x, self.qkv_p), positions, md, cos_sin, kv)
+        return _proj_out_w8(self.drop(a), self.o_p, ws)
 
     def attend(self, qkv: torch.Tensor, positions: torch.Tensor, md: attn_ops.AttnMetadata, cos_sin: torch.Tensor,
                kv: Tuple[torch.Tensor, torch.Tensor]) -> torch.Tensor:
@@ -210,6 +253,8 @@ class LlamaMLP(nn.Module):
         self.gate_up_pf = None  # block-packed with ln2 folded in (FOLD_NORM)
 
     def forward(self, x: torch.Tensor, ws: Optional[torch.Tensor] = None):
+        if isinstance(self.gate_up_p, gemm_w8.W8):  # FP8 weights (ln2 folded into gate_up)
+            return _proj_out_w8(gemm_w8.linear_silu(x, self.gate_up_p, ws), self.down_p, ws)
         h = gemm.linear_silu(x, self.gate_up, ws, packed=self.gate_up_p)  # gate/up rows interleaved by 16
         return _proj_out(h, self.down, ws, self.down_p)
 
@@ -256,6 +301,10 @@ class LlamaForCausalLM(nn.Module):
         self.norm = None
         self.lm_head = None
         self.lm_head_p = None  # block-packed decode copy (pack_decode_weights)
+        # projection weight element type: "bf16", or "fp8" (weight-only OCP e4m3, one scale per output
+        # channel: pack_decode_weights quantises; set before it runs -- README "Weight dtype")
+        self.weight_dtype = "bf16"
+        self.w8 = False  # the projections are gemm_w8.W8 handles
         self.register_buffer("cos_sin", reference.rope_cos_sin_cache(cfg.max_position, cfg.head_dim, cfg.rope_theta,
                                                                       cfg.rope_scaling, device=self.device),
                              persistent=False)
@@ -504,7 +553,10 @@ class LlamaForCausalLM(nn.Module):
             # profiles/r2_decode_ab.txt: fewer fp32 slab bytes written and re-read); the residual
             # update inside the O launch (1 % slower, profiles/r4_o_inlaunch_ab.jsonl) and as phase 0
             # of the fused launches (3 % slower, profiles/r5_phase_ab.jsonl) were removed in round 6
-            o = gemm.linear_partial(a, layer.attn.o, ws, packed=layer.attn.o_p, half=True)
+            if self.w8:
+                o = gemm_w8.linear_partial(a, layer.attn.o_p, ws, half=True)
+            else:
+                o = gemm.linear_partial(a, layer.attn.o, ws, packed=layer.attn.o_p, half=True)
             parts = gemm.residual_parts(o, residual, buf2)
             pending = self._decode_mlp(layer, residual, parts, ws)
         x, _ = gemm.partial_add_rms_norm(pending, residual, self.norm, self.cfg.rms_eps)
@@ -517,6 +569,8 @@ class LlamaForCausalLM(nn.Module):
         # fallback only at TP = 1 -- a TP group cannot re-run one rank's step, llm_engine.py)
         # kc: the K cache the step writes (ops/attention.py slab_writers_ok)
         if kc is not None and not attn_ops.slab_writers_ok(kc):
+            return False
+        if self.w8:  # FP8 weights: the two-launch forms only (the fused launches are bf16-only)
             return False
         return (md.num_prefill == 0 and gemm.QKV_ATTN_FUSED and at.nkv >= gemm.QKV_ATTN_MIN_KV
                 and gemm.fused_rows_ok(T, nparts) and md.num_decode == T
@@ -537,8 +591,11 @@ class LlamaForCausalLM(nn.Module):
         # (64-row n-blocks at half the split: half the slabs the attention prologue sums -- the 70B
         # TP=8 shard's 10 n-blocks otherwise take split 16; one 64-row tile only: the row-tiled wide
         # batches keep 128-row n-blocks, 8B at 256 rows 34.5 vs 26 us, profiles/r5_wide_256_kgrid.md)
-        p = gemm.linear_partial_rowscale(residual, at.qkv, ws, rs, packed=at.qkv_pf,
-                                         half=gemm.QKV_HALF and T <= gemm.SKINNY_MAX_M)
+        half = gemm.QKV_HALF and T <= gemm.SKINNY_MAX_M
+        if self.w8:
+            p = gemm_w8.linear_partial_rowscale(residual, at.qkv_pf, ws, rs, half=half)
+        else:
+            p = gemm.linear_partial_rowscale(residual, at.qkv, ws, rs, packed=at.qkv_pf, half=half)
         if md.num_prefill == 0:
             return attn_ops.paged_decode_from_qkv(p, positions, self.cos_sin, kc, vc, md, at.scale, at.nq, at.nkv,
                                                   k_scale=at.k_scale, v_scale=at.v_scale)
@@ -550,6 +607,9 @@ class LlamaForCausalLM(nn.Module):
         """Folded-norm gate_up + SiLU and the down projection of one layer -> down's split-K slabs."""
         mlp = layer.mlp
         rs = gemm.RowScale(parts, layer.eps)
+        if self.w8:  # FP8 weights: gate_up + SiLU, then down, as two W8 launches
+            h = gemm_w8.linear_silu(residual, mlp.gate_up_pf, ws=self._ws_gu, rowscale=rs)
+            return gemm_w8.linear_down(h, mlp.down_p, ws)
         if gemm.mlp_fused_ok(residual, mlp.gate_up_pf, mlp.down_p, parts.shape[0]) and not self.st.shared_device:
             # gate_up + SiLU and the down slabs in one launch (down's launch ramp hidden)
             return gemm.mlp_fused(residual, mlp.gate_up_pf, mlp.down_p, rs, ws, self._flow)
@@ -809,7 +869,15 @@ class LlamaForCausalLM(nn.Module):
         attributes become shape-only (meta) placeholders.  With folded norms (Llama MLP) the
         packed-only copies of QKV and gate/up carry their RMSNorm weight, and prefill normalises
         with unit weights (``ln1`` / ``ln2`` become ones; the originals stay as ``ln*_folded``).
-        ``POLYKEY_PACKED_WEIGHTS`` = auto | 1 (both copies) | packed (packed only) | 0."""
+        ``POLYKEY_PACKED_WEIGHTS`` = auto | 1 (both copies) | packed (packed only) | 0.
+
+        With ``weight_dtype == "fp8"`` the projections are quantised instead
+        (:meth:`_quantise_projections`), on any device and whatever that variable says."""
+        if self.w8 and self.weight_dtype != "fp8":
+            raise ValueError("this model's projections are already FP8 (weight_dtype=fp8); it cannot serve "
+                             f"weight_dtype={self.weight_dtype}")
+        if self.weight_dtype == "fp8":
+            return self._quantise_projections()
         mode = mode or os.environ.get("POLYKEY_PACKED_WEIGHTS", "auto")
         if mode == "0" or self.device.type != "cuda" or not gemm.SKINNY_ENABLED:
             return False
@@ -853,6 +921,82 @@ class LlamaForCausalLM(nn.Module):
         self.packed_only = packed_only
         self._ones_h = torch.ones(self.cfg.hidden_size, dtype=self.lm_head.dtype, device=self.device)
         return True
+
+    def _quantise_projections(self) -> bool:
+        """``weight_dtype="fp8"``: the four dense projections of every layer become weight-only
+        FP8 (:class:`gemm_w8.W8`: block-packed OCP e4m3 bytes, one fp32 scale per output channel),
+        quantised once, after the RMSNorm fold: ``qkv_pf`` / ``gate_up_pf`` =
+        quantise(fold_norm(w, ln)) -- one rounding -- and o / down unfolded.  As in the packed-only
+        mode the row-major attributes become meta placeholders, freed projection by projection,
+        and ``ln1`` / ``ln2`` become ones (the originals stay as ``ln*_folded``).  Embedding, LM
+        head and norm weights stay bf16.  On the GPU the widen scratch of the prefill path (the
+        largest projection, bf16) is reserved here, before the KV cache is sized.  Works on any
+        device: CPU tensors take the fp32 reference ops."""
+        if self.w8:  # already quantised (a model handed from one engine to the next)
+            return True
+        if self.st.tp_size > 1 or self.st.ep_size > 1:
+            raise ValueError(f"weight_dtype=fp8 does not support tp={self.st.tp_size} / ep={self.st.ep_size}: "
+                             "FP8 weights are not sharded (use weight_dtype=bf16)")
+        if not isinstance(self.layers[0].mlp, LlamaMLP):
+            raise ValueError("weight_dtype=fp8 does not support MoE models: the grouped expert GEMMs are "
+                             "bf16-only (use weight_dtype=bf16)")
+        l0 = self.layers[0]
+        for w in (l0.attn.qkv, l0.attn.o, l0.mlp.gate_up, l0.mlp.down):
+            if w.shape[0] % 128 or w.shape[1] % 256:
+                raise ValueError(f"weight_dtype=fp8 needs projections of N % 128 == 0 and K % 256 == 0 "
+                                 f"(got {tuple(w.shape)})")
+
+        def quantise(owner, name: str, norm_w: Optional[torch.Tensor] = None) -> gemm_w8.W8:
+            src = getattr(owner, name)
+            out = gemm_w8.W8.from_weight(src if norm_w is None else gemm.fold_norm(src, norm_w))
+            setattr(owner, name, _p(torch.empty(src.shape, dtype=src.dtype, device="meta")))
+            return out
+
+        largest = 0
+        for layer in self.layers:
+            at, mlp = layer.attn, layer.mlp
+            at.qkv_pf = at.qkv_p = quantise(at, "qkv", layer.ln1)
+            mlp.gate_up_pf = mlp.gate_up_p = quantise(mlp, "gate_up", layer.ln2)
+            layer.ln1_folded, layer.ln2_folded = layer.ln1, layer.ln2
+            layer.ln1 = _p(torch.ones_like(layer.ln1))
+            layer.ln2 = _p(torch.ones_like(layer.ln2))
+            at.o_p = quantise(at, "o")
+            mlp.down_p = quantise(mlp, "down")
+            largest = max([largest] + [w.shape[0] * w.shape[1] for w in (at.qkv_p, at.o_p, mlp.gate_up_p, mlp.down_p)])
+        cuda = self.device.type == "cuda"
+        if cuda and self.lm_head.shape[0] % 128 == 0 and self.lm_head.shape[1] % 256 == 0 and gemm.SKINNY_ENABLED:
+            self.lm_head_p = gemm.pack_weight(self.lm_head)
+        # the prefill path's widen scratch: one buffer the size of the largest projection, owned by
+        # the model and shared by its handles (fixed address for the model's lifetime)
+        self._w8_scratch = torch.empty(largest, dtype=torch.bfloat16, device=self.device) if cuda else None
+        for layer in self.layers:
+            for h in (layer.attn.qkv_p, layer.attn.o_p, layer.mlp.gate_up_p, layer.mlp.down_p):
+                h.scratch = self._w8_scratch
+        self.w8 = True
+        self.packed_only = True
+        self._ones_h = torch.ones(self.cfg.hidden_size, dtype=self.lm_head.dtype, device=self.device)
+        logging.getLogger(__name__).info(
+            "weights: dtype fp8 (e4m3, per-channel scales), %d projection bytes, %d widen-scratch bytes",
+            self.projection_bytes(), self.w8_scratch_bytes())
+        return True
+
+    def w8_scratch_bytes(self) -> int:
+        t = getattr(self, "_w8_scratch", None)
+        return 0 if t is None else t.numel() * t.element_size()
+
+    def projection_bytes(self) -> int:
+        """Bytes the layers' projection tensors hold: every matrix reachable from a layer's
+        attention / MLP (row-major, packed and quantised copies; a tensor reachable twice counts
+        once; meta placeholders hold nothing)."""
+        held = {}  # data_ptr -> bytes
+        for layer in self.layers:
+            for owner in (layer.attn, layer.mlp):
+                for v in list(vars(owner).values()) + list(owner._parameters.values()):
+                    tensors = (v.packed, v.scale) if isinstance(v, gemm_w8.W8) else (v,)
+                    for t in tensors:
+                        if isinstance(t, torch.Tensor) and not t.is_meta and (t.dim() >= 2 or t is not v):
+                            held[t.data_ptr()] = t.numel() * t.element_size()
+        return sum(held.values())
 
     def _packed_prefill_ok(self) -> bool:
         """Every dense projection is a shape the packed-W prefill GEMM tiles (Llama MLP; per-rank

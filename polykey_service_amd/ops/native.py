@@ -75,6 +75,10 @@ SIGNATURES = {
     "pk_copy_from_host": [P, P, I64, P],
     "pk_residual_parts": [P, P, I32, I32, I32, P, P],
     "pk_car_gemm": [P, P, I32, P, P, I32, I32, P, I32, I32, P, P],
+    # weight-only FP8 projections (csrc/kernels/gemm_w8.hip)
+    "pk_w8_gemm": [P, P, P, P, P, I32, I32, I32, I32, I32, I32, I32, P, I32, F32, P],
+    "pk_w8_widen": [P, P, I32, I32, P],
+    "pk_col_scale": [P, P, I32, I32, I32, P],
 }
 
 

@@ -143,6 +143,38 @@ def dequantize_fp8(c: torch.Tensor, scale: float = 1.0) -> torch.Tensor:
     return c.float() * scale
 
 
+def quantize_fp8_rows(w: torch.Tensor):
+    """Weight-only FP8 of a ``[N, K]`` projection: one fp32 scale per row (output channel),
+    ``scale[n] = max|w[n, :]| / 448`` (an all-zero row: 1.0), bytes = :func:`quantize_fp8` of
+    ``w / scale``.  Returns (bytes ``[N, K]`` e4m3, scale ``[N]`` fp32).
+
+    Both quotients are formed in float64 and rounded to fp32, which IS the correctly rounded fp32
+    quotient (53 >= 2 * 24 + 2 bits: the second rounding is innocuous), so every device produces
+    the bytes the CPU's IEEE division does -- a GPU's own fp32 division may be an ulp off."""
+    amax = w.float().abs().amax(dim=1)
+    scale = torch.where(amax > 0, (amax.double() / FP8_MAX).float(), torch.ones_like(amax))
+    out = torch.empty(w.shape, dtype=FP8, device=w.device)
+    rows = 2048  # bounds the float64 temporary of a large projection
+    for r in range(0, w.shape[0], rows):
+        q = (w[r:r + rows].double() / scale[r:r + rows].double()[:, None]).float()
+        out[r:r + rows] = q.clamp(-FP8_MAX, FP8_MAX).to(FP8)
+    return out, scale
+
+
+def w8_linear(x: torch.Tensor, b: torch.Tensor, scale: torch.Tensor, rinv: Optional[torch.Tensor] = None,
+              dtype=torch.float32) -> torch.Tensor:
+    """The function every W8 projection computes, before its epilogue's rounding:
+    ``y[m, n] = (sum_k x[m, k] * widen(b[n, k])) * scale[n]`` (times ``rinv[m]`` with the folded
+    norm), products and sums in ``dtype`` (fp32: the ops' CPU path; float64: the tests' reference).
+    ``b``: row-major e4m3 ``[N, K]``."""
+    y = (x.to(dtype) @ b.to(dtype).t()) * scale.to(dtype)[None, :]
+    return y if rinv is None else y * rinv.to(dtype)[:, None]
+
+
+def w8_linear_f64(x, b, scale, rinv=None) -> torch.Tensor:
+    return w8_linear(x, b, scale, rinv, dtype=torch.float64)
+
+
 def _store(cache_flat: torch.Tensor, index: tuple, rows: torch.Tensor, scale: float) -> None:
     """cache_flat[index] = rows in the cache's dtype (FP8 caches: quantised, indexed as bytes)."""
     if cache_flat.dtype == FP8:
