@@ -48,9 +48,15 @@ def _status():
 class LLMTool:
     requires_secret = False
 
-    def __init__(self, name: str, model_name: str, llm, chat: bool):
+    def __init__(self, name: str, model_name: str, llm, chat: bool, lora: Optional[str] = None,
+                 parent: Optional[str] = None, lora_names: tuple = ()):
         self.name = name
         self.model_name = model_name
+        # an adapter's tool (``llm.chat:<adapter>``): the base model's engine with ``lora`` set on
+        # every request; ``lora_names``: the adapters ``parameters.lora`` may name on this tool
+        self.lora = lora
+        self.parent = parent
+        self.lora_names = tuple(lora_names)
         self.llm = llm
         self.chat = chat
         self.tok = llm.tokenizer
@@ -77,10 +83,15 @@ class LLMTool:
             sp.validate(1 << 30)
         except (ValueError, TypeError) as e:
             raise ToolError("INVALID_ARGUMENT", str(e))
+        if self.lora is not None:
+            sp.lora = self.lora
+        elif sp.lora is not None and sp.lora not in self.lora_names:
+            raise ToolError("NOT_FOUND", f"LoRA adapter {sp.lora!r} is not served by model {self.model_name!r}; "
+                                         f"available: {sorted(self.lora_names)}")
         return sp
 
     def _summary(self, text: str, n_prompt: int, toks: List[int], last, t0: float, with_ids: bool = False,
-                 lps: Optional[list] = None) -> dict:
+                 lps: Optional[list] = None, lora: Optional[str] = None) -> dict:
         m = (last.metrics or {}) if last is not None else {}
         out = {
             "model": self.model_name,
@@ -93,6 +104,8 @@ class LLMTool:
             "metrics": {k: v for k, v in {**m, "server_e2e_s": time.monotonic() - t0, "server_t0": t0}.items()
                         if v is not None},
         }
+        if lora is not None:  # the LoRA adapter the request ran on
+            out["lora"] = lora
         if with_ids:  # parameters.return_token_ids: the generated ids themselves (token-level clients, tests)
             out["token_ids"] = list(toks)
         if lps is not None:
@@ -139,7 +152,8 @@ class LLMTool:
         if params.get("return") == "struct" or oc.tool_calls or oc.executed:
             m = oc.metrics or {}
             resp.struct_output.update({
-                "model": self.model_name, "text": oc.content, "tool_calls": oc.tool_calls,
+                "model": self.model_name, **({"lora": sp.lora} if sp.lora is not None else {}),
+                "text": oc.content, "tool_calls": oc.tool_calls,
                 "tool_results": oc.executed, "finish_reason": oc.finish_reason,
                 "usage": {"prompt_tokens": oc.prompt_tokens, "completion_tokens": oc.completion_tokens,
                           "total_tokens": oc.prompt_tokens + oc.completion_tokens},
@@ -178,7 +192,7 @@ class LLMTool:
         resp = proto.ExecuteToolResponse(status=_status())
         if params.get("return") == "struct":
             resp.struct_output.update(self._summary(text, len(prompt), toks, last, t0,
-                                                    bool(params.get("return_token_ids")), lps))
+                                                    bool(params.get("return_token_ids")), lps, sp.lora))
         else:
             resp.string_output = text
         return resp
@@ -221,7 +235,7 @@ class LLMTool:
         text = detok.text
         final = proto.ExecuteToolResponse(status=_status())
         final.struct_output.update(self._summary(text, len(prompt), toks, last, t0,
-                                                 bool(params.get("return_token_ids")), lps))
+                                                 bool(params.get("return_token_ids")), lps, sp.lora))
         yield final
 
 
@@ -494,12 +508,24 @@ def attach_model_groups(router, cfg, logger, timeout_s: float = 600.0) -> Option
     return router.llm
 
 
-def _register_tools(router, cfg, llm) -> None:
+def _register_tools(router, cfg, llm, lora_names=None) -> None:
+    """The model's two tools, and two more per LoRA adapter (``llm.generate:<adapter>`` /
+    ``llm.chat:<adapter>``: the same engine with that adapter).  An adapter named like a served
+    model is refused."""
+    from ..config.server_config import parse_lora_modules
     name = cfg.model if isinstance(cfg.model, str) else "model"
-    router.register_model_tool("llm.generate", name, LLMTool("llm.generate", name, llm, chat=False))
-    chat_tool = LLMTool("llm.chat", name, llm, chat=True)
-    chat_tool.router = router
-    router.register_model_tool("llm.chat", name, chat_tool)
+    if lora_names is None:
+        lora_names = [n for n, _ in parse_lora_modules(getattr(cfg, "lora_modules", ""))]
+    loras = tuple(lora_names)
+    for ad in loras:
+        if ad == name or ad in router.models("llm.chat") or ad in router.models("llm.generate"):
+            raise ValueError(f"LoRA adapter name {ad!r} collides with a served model name")
+    for ad in (None,) + loras:
+        for fam, chat in (("llm.generate", False), ("llm.chat", True)):
+            tool = LLMTool(fam, ad or name, llm, chat=chat, lora=ad, parent=name if ad else None, lora_names=loras)
+            if chat:
+                tool.router = router
+            router.register_model_tool(fam, ad or name, tool)
 
 
 def attach_local_llm(router, cfg, logger, engine=None, llm=None):
@@ -555,10 +581,11 @@ def attach_local_llm(router, cfg, logger, engine=None, llm=None):
                 raise SystemExit(0)
             llm = pool
     name = cfg.model if isinstance(cfg.model, str) else "model"
-    router.register_model_tool("llm.generate", name, LLMTool("llm.generate", name, llm, chat=False))
-    chat_tool = LLMTool("llm.chat", name, llm, chat=True)
-    chat_tool.router = router
-    router.register_model_tool("llm.chat", name, chat_tool)
+    try:
+        _register_tools(router, cfg, llm, getattr(engine, "lora_names", None))
+    except ValueError:  # an adapter named like a served model: nothing stays running
+        llm.shutdown()
+        raise
     router.llm = llm
     logger.info("local LLM backend ready", model=name, kv_blocks=engine.runner.num_blocks,
                 block_size=engine.cfg.block_size, tp=engine.st.tp_size,

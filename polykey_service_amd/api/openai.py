@@ -68,6 +68,12 @@ def _llm(router, model: Optional[str]):
     return tool.llm, tool.model_name
 
 
+def _lora(router, model: Optional[str]) -> Optional[str]:
+    """The LoRA adapter ``model`` names (an adapter is served as a model of its own), or None."""
+    tool = router.resolve("llm.chat" + (f":{model}" if model else ""), {})
+    return getattr(tool, "lora", None)
+
+
 def _params(body: Dict[str, Any], chat: bool = True) -> SamplingParams:
     d = {k: body[k] for k in _SAMPLING_KEYS if k in body and body[k] is not None}
     d["logprobs"] = lpf.parse_openai(body, chat)
@@ -109,13 +115,20 @@ def create_app(router):
     @app.get("/v1/models")
     async def models():
         now = int(time.time())
-        return {"object": "list", "data": [{"id": m, "object": "model", "created": now, "owned_by": "polykey"}
-                                           for m in router.models("llm.chat")]}
+        data = []
+        for m in router.models("llm.chat"):
+            entry = {"id": m, "object": "model", "created": now, "owned_by": "polykey"}
+            parent = getattr(router.resolve(f"llm.chat:{m}", {}), "parent", None)
+            if parent is not None:  # a LoRA adapter of that base model
+                entry["parent"] = parent
+            data.append(entry)
+        return {"object": "list", "data": data}
 
     async def _run(body: Dict[str, Any], chat: bool):
         try:
             llm, model = _llm(router, body.get("model"))
             sp = _params(body, chat)
+            sp.lora = _lora(router, body.get("model"))
         except ToolError as e:
             return err(404 if e.code == "NOT_FOUND" else 503, e.message)
         except (ValueError, TypeError) as e:

@@ -43,6 +43,10 @@ class ServerConfig:
     num_kv_blocks: int = 0         # 0 → size from free HBM
     kv_cache_dtype: str = "auto"   # auto | bf16 | fp8 (alias fp8_e4m3): KV-cache element type
     weight_dtype: str = "auto"     # auto | bf16 | fp8 (alias fp8_e4m3): projection weight element type
+    # LoRA adapters served next to the model: "name=path[,name=path...]" (PEFT directories), all
+    # resident; OpenAI "model": "<name>" / "llm.chat:<name>" / parameters.lora pick one
+    lora_modules: str = ""
+    max_lora_rank: int = 64
     hip_graphs: bool = True
     device: str = "cuda"
     seed: int = 0
@@ -79,6 +83,8 @@ _ENV = {
     "num_kv_blocks": "POLYKEY_NUM_KV_BLOCKS",
     "kv_cache_dtype": "POLYKEY_KV_CACHE_DTYPE",
     "weight_dtype": "POLYKEY_WEIGHT_DTYPE",
+    "lora_modules": "POLYKEY_LORA_MODULES",
+    "max_lora_rank": "POLYKEY_MAX_LORA_RANK",
     "hip_graphs": "POLYKEY_HIP_GRAPHS",
     "device": "POLYKEY_DEVICE",
     "seed": "POLYKEY_SEED",
@@ -123,6 +129,22 @@ def env_weight_dtype(environ: Optional[Mapping[str, str]] = None) -> str:
     return (os.environ if environ is None else environ).get(_ENV["weight_dtype"], "") or "auto"
 
 
+def parse_lora_modules(spec) -> tuple:
+    """``--lora-modules`` / ``POLYKEY_LORA_MODULES``: "name=path[,name=path...]" -> ((name, path), ...);
+    a tuple of pairs passes through."""
+    if not isinstance(spec, str):
+        return tuple((str(n), p) for n, p in (spec or ()))
+    out = []
+    for item in filter(None, (s.strip() for s in spec.split(","))):
+        name, sep, path = item.partition("=")
+        if not sep or not name.strip() or not path.strip():
+            raise ValueError(f"lora_modules entries must be name=path (got {item!r})")
+        out.append((name.strip(), path.strip()))
+    if len({n for n, _ in out}) != len(out):
+        raise ValueError(f"lora_modules names must be unique (got {[n for n, _ in out]})")
+    return tuple(out)
+
+
 def _flag_name(field: str) -> str:
     return field.replace("_", "-")
 
@@ -165,4 +187,5 @@ def load_server_config(argv: Optional[Sequence[str]] = None,
         setattr(cfg, fname, val)
     cfg.kv_cache_dtype = normalize_kv_cache_dtype(cfg.kv_cache_dtype)
     cfg.weight_dtype = normalize_weight_dtype(cfg.weight_dtype)
+    parse_lora_modules(cfg.lora_modules)  # a malformed list fails at start-up
     return cfg

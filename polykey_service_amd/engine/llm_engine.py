@@ -16,7 +16,8 @@ from typing import Callable, Dict, Iterable, List, Optional
 import torch
 
 from .._native.loader import load_extension
-from ..config.server_config import env_weight_dtype, normalize_kv_cache_dtype, normalize_weight_dtype
+from ..config.server_config import (env_weight_dtype, normalize_kv_cache_dtype, normalize_weight_dtype,
+                                    parse_lora_modules)
 from ..models import build_model
 from ..models.config import ModelConfig, get_config
 from ..ops.sampler import logprob_entry
@@ -65,6 +66,11 @@ class EngineConfig:
     # automatic prefix caching (csrc/runtime/block_manager.h); POLYKEY_PREFIX_CACHING=0 disables
     prefix_caching: bool = dataclasses.field(
         default_factory=lambda: os.environ.get("POLYKEY_PREFIX_CACHING", "1") != "0")
+    # LoRA adapters served next to the base model: (name, PEFT directory) pairs -- or (name,
+    # models.lora.LoraAdapter) for adapters built in memory -- all resident, one slot each (README
+    # "LoRA adapters"); a request picks one with SamplingParams.lora.  () = off: nothing changes
+    lora_modules: tuple = ()
+    max_lora_rank: int = 64
 
     @classmethod
     def from_server_config(cls, sc) -> "EngineConfig":
@@ -73,7 +79,9 @@ class EngineConfig:
                    max_num_batched_tokens=sc.max_num_batched_tokens, max_model_len=sc.max_model_len,
                    num_kv_blocks=sc.num_kv_blocks, gpu_mem_fraction=sc.gpu_mem_fraction, hip_graphs=sc.hip_graphs,
                    num_layers=getattr(sc, "num_layers", 0), kv_cache_dtype=getattr(sc, "kv_cache_dtype", "auto"),
-                   weight_dtype=getattr(sc, "weight_dtype", "auto"))
+                   weight_dtype=getattr(sc, "weight_dtype", "auto"),
+                   lora_modules=parse_lora_modules(getattr(sc, "lora_modules", "")),
+                   max_lora_rank=getattr(sc, "max_lora_rank", 64))
 
 
 def tokenizer_for(cfg: EngineConfig, mcfg: Optional[ModelConfig] = None):
@@ -101,6 +109,20 @@ class LLMEngine:
                 raise ValueError(f"weight_dtype=fp8 does not support tp={self.st.tp_size}: FP8 weights are not sharded")
             if self.st.ep_size > 1:
                 raise ValueError(f"weight_dtype=fp8 does not support ep={self.st.ep_size}: FP8 weights are not sharded")
+        if cfg.lora_modules:
+            # adapters cover the dense Llama projections in bf16 on one GPU; no silent fallback
+            if mcfg.is_moe:
+                raise ValueError(f"LoRA adapters do not support MoE models ({mcfg.name}) yet: the expert "
+                                 "projections have no adapter path (a follow-up)")
+            if self.st.tp_size > 1:
+                raise ValueError(f"LoRA adapters do not support tp={self.st.tp_size} yet: adapters are not "
+                                 "sharded (a follow-up)")
+            if self.st.ep_size > 1:
+                raise ValueError(f"LoRA adapters do not support ep={self.st.ep_size} yet: adapters are not "
+                                 "sharded (a follow-up)")
+            if cfg.weight_dtype == "fp8":
+                raise ValueError("LoRA adapters do not support weight_dtype=fp8 yet: the W8 chain has no "
+                                 "adapter path (a follow-up; use weight_dtype=bf16)")
         if cfg.num_layers > 0 and cfg.num_layers != mcfg.num_layers:
             mcfg = dataclasses.replace(mcfg, num_layers=cfg.num_layers)
         if cfg.max_model_len > mcfg.max_position:
@@ -158,6 +180,13 @@ class LLMEngine:
         if cfg.weight_dtype != "fp8":
             logging.getLogger(__name__).info("weights: dtype %s, %d projection bytes, 0 widen-scratch bytes",
                                              cfg.weight_dtype, self.weight_bytes)
+        # LoRA adapters: loaded and made resident here, before the KV cache is sized
+        self.lora_names: List[str] = []
+        self.lora_bytes = 0
+        if cfg.lora_modules:
+            self._load_adapters(model, mcfg)
+        elif getattr(model, "lora", None) is not None:
+            model.lora = None  # a model handed over from an engine that served adapters
         self.tokenizer = tokenizer_for(cfg, mcfg)
         rcfg = RunnerConfig(block_size=cfg.block_size, max_num_seqs=cfg.max_num_seqs,
                             max_num_batched_tokens=cfg.max_num_batched_tokens, max_model_len=cfg.max_model_len,
@@ -196,6 +225,24 @@ class LLMEngine:
         self.before_schedule: Optional[Callable[[], None]] = None
         self.continuation_steps = 0
 
+    def _load_adapters(self, model, mcfg: ModelConfig) -> None:
+        from ..models.lora import MAX_SLOTS, LoraAdapter
+        cfg = self.cfg
+        if not hasattr(model, "enable_lora"):
+            raise ValueError(f"LoRA adapters are not supported by {type(model).__name__}")
+        if len(cfg.lora_modules) > MAX_SLOTS:
+            raise ValueError(f"at most {MAX_SLOTS} LoRA adapters can be served by one engine "
+                             f"(got {len(cfg.lora_modules)})")
+        adapters = []
+        for name, src in cfg.lora_modules:
+            ad = src if isinstance(src, LoraAdapter) else LoraAdapter.load(str(src), mcfg, cfg.max_lora_rank)
+            adapters.append((str(name), ad))
+        state = model.enable_lora(adapters, cfg.max_lora_rank, max(cfg.max_num_batched_tokens, cfg.max_num_seqs))
+        self.lora_names = list(state.names)
+        self.lora_bytes = state.nbytes
+        logging.getLogger(__name__).info("LoRA adapters: %d resident (%s), max rank %d, %d bytes",
+                                         len(state.names), ", ".join(state.names), cfg.max_lora_rank, state.nbytes)
+
     def _serving_preflight(self, mcfg: ModelConfig) -> None:
         """TP: the fused decode collective checked at the shape serving will replay it at (the
         largest decode graph bucket x hidden, 16 back-to-back calls, graph-replayed) before any
@@ -224,6 +271,9 @@ class LLMEngine:
             raise ValueError("prompt token id out of range")
         if any(not 0 <= t < self.mcfg.vocab_size for t, _ in params.logit_bias):
             raise ValueError("logit_bias token id out of range")
+        if params.lora is not None and params.lora not in self.lora_names:
+            raise ValueError(f"unknown LoRA adapter {params.lora!r}: this engine serves "
+                             f"{', '.join(self.lora_names) if self.lora_names else 'no adapters'}")
         g = self._grammar(params)
         seq = Sequence(request_id or uuid.uuid4().hex, prompt_ids, params, self.mcfg.eos_token_id, user)
         if g is None:

@@ -66,15 +66,17 @@ class RunnerConfig:
 class _Layout:
     """Fixed offsets of every per-step int32 section inside one staging buffer."""
 
-    def __init__(self, max_tokens: int, max_seqs: int, max_blocks: int):
+    def __init__(self, max_tokens: int, max_seqs: int, max_blocks: int, lora: bool = False):
         self.max_tokens, self.max_seqs, self.max_blocks = max_tokens, max_seqs, max_blocks
         off = 0
         self.sections = {}
+        # "lora_idx": the adapter slot of every TOKEN row (-1: none); only with adapters configured
         for name, n in (("header", 16), ("input_ids", max_tokens), ("positions", max_tokens), ("slots", max_tokens),
                         ("context_lens", max_seqs), ("cu_q", max_seqs + 1), ("cu_rel", max_seqs + 1), ("sample_idx", max_seqs),
                         ("temperature", max_seqs), ("top_k", max_seqs), ("top_p", max_seqs), ("min_p", max_seqs),
                         ("seeds", max_seqs), ("offsets", max_seqs), ("pen_slot", max_seqs), ("rep", max_seqs),
                         ("freq", max_seqs), ("pres", max_seqs), ("logprobs", max_seqs),
+                        *((("lora_idx", max_tokens),) if lora else ()),
                         ("block_tables", max_seqs * max_blocks)):
             self.sections[name] = (off, n)
             off += (n + 15) // 16 * 16  # 64-byte aligned sections
@@ -109,7 +111,10 @@ class ModelRunner:
         self.bs = cfg.block_size
         self.max_blocks = (cfg.max_model_len + self.bs - 1) // self.bs
         self.max_step_tokens = cfg.max_num_batched_tokens  # decodes count toward the budget
-        self.layout = _Layout(self.max_step_tokens, cfg.max_num_seqs, self.max_blocks)
+        # resident LoRA adapters (models/lora.py LoraState; the engine enables them on the model
+        # before it builds the runner): a per-token slot section and a LoRA variant of every graph
+        self.lora = getattr(model, "lora", None)
+        self.layout = _Layout(self.max_step_tokens, cfg.max_num_seqs, self.max_blocks, lora=self.lora is not None)
         pin = device.type == "cuda"
         # two pinned staging buffers used alternately: a step may be packed while the previous
         # step's H2D copy is still queued behind the GPU (continuation launches, LLMEngine.step)
@@ -121,6 +126,9 @@ class ModelRunner:
         self.host_buf, self.h = self._host_bufs[0], self._hs[0]
         self.dev_buf = torch.zeros(self.layout.size, dtype=torch.int32, device=device)
         self.d = {k: self.layout.view(self.dev_buf, k) for k in self.layout.sections}
+        if self.lora is not None:
+            self.lora.idx = self.d["lora_idx"]  # the kernels read the staged section itself
+        self._step_lora = 0  # the step being packed has a row with an adapter
         self._tok_hosts = [torch.zeros(cfg.max_num_seqs, dtype=torch.int32, pin_memory=pin) for _ in range(2)]
         self._tok_events = [None, None]
         # per-token logprobs (ops/sampler.py logprobs): one packed record per sampling row, written
@@ -162,12 +170,19 @@ class ModelRunner:
         self.graph_out: Dict[int, torch.Tensor] = {}
         self.short_graphs: Dict[int, torch.cuda.CUDAGraph] = {}
         self.short_graph_out: Dict[int, torch.Tensor] = {}
+        # LoRA variants of both, captured only with adapters configured; a step replays them when
+        # one of its decode rows has an adapter, today's graphs otherwise
+        self.lora_graphs: Dict[int, torch.cuda.CUDAGraph] = {}
+        self.lora_graph_out: Dict[int, torch.Tensor] = {}
+        self.lora_short_graphs: Dict[int, torch.cuda.CUDAGraph] = {}
+        self.lora_short_graph_out: Dict[int, torch.Tensor] = {}
         self.short_ctx = attn_ops._PART if cfg.max_model_len > attn_ops._PART else 0
         self.graph_pool = None
         a0 = model.layers[0].attn
         self.part_o, self.part_ml = attn_ops.decode_workspace(cfg.max_num_seqs, a0.nq, self.max_blocks, self.bs, device,
                                                               kv_heads=a0.nkv)
-        self.stats = {"steps": 0, "graph_steps": 0, "short_graph_steps": 0, "tokens": 0, "seed_msgs": 0}
+        self.stats = {"steps": 0, "graph_steps": 0, "short_graph_steps": 0, "tokens": 0, "seed_msgs": 0,
+                      "lora_steps": 0, "lora_graph_steps": 0}
         self.keep_logits = False  # tests: keep the last eager step's logits
         self.last_logits = None
         # diagnostics (tools/tp_rehearsal.py): every step's logits, graphed steps included (a copy
@@ -272,6 +287,8 @@ class ModelRunner:
         h = self.h
         T = self.bm.pack_step(sids, ncomp, nnew, tok_arr, h["input_ids"], h["positions"], h["slots"],
                               h["block_tables"], self.max_blocks, h["context_lens"], h["cu_q"])
+        if self.lora is not None:
+            self._fill_lora(seqs, T)
         # sampling rows: hidden-state row index of each sampling sequence
         pos_of = {s.seq_id: int(h["cu_q"][i + 1]) - 1 for i, s in enumerate(seqs)}
         h["logprobs"][:len(sampling)] = -1  # rows that ask overwrite theirs below
@@ -293,6 +310,22 @@ class ModelRunner:
                 h["logprobs"][r] = p.logprobs
                 want_lp = True
         return T, n, want_lp
+
+    # ------------------------------------------------------------------ LoRA
+    def _fill_lora(self, seqs: List[Sequence], T: int) -> None:
+        """Section "lora_idx": the adapter slot of every token row of the packed step (the rows of
+        sequence i are cu_q[i] .. cu_q[i + 1]), -1 for base rows.  Sets ``_step_lora``."""
+        h = self.h
+        li, cu = h["lora_idx"], h["cu_q"]
+        li[:T] = -1
+        any_lora = 0
+        slot_of = self.lora.slot_of
+        for i, s in enumerate(seqs):
+            name = s.params.lora
+            if name is not None:
+                li[int(cu[i]):int(cu[i + 1])] = slot_of[name]
+                any_lora = 1
+        self._step_lora = any_lora
 
     # ------------------------------------------------------------------ penalties
     def _neutral_penalties(self, n: int) -> None:
@@ -513,7 +546,8 @@ class ModelRunner:
 
     # ----------------------------------------------------------------- execute
     # header words (section "header"): mode, T, n, nd, ns, max_q, graph bucket, short-context graph,
-    # continuation (input ids = the previous step's sampled ids, already on the device)
+    # continuation (input ids = the previous step's sampled ids, already on the device), LoRA form
+    # (a row of the step has an adapter)
     # MODE_SEED: header = (mode, id words, entries); seeds penalty slots (_seed_penalties)
     # MODE_GLOAD: header = (mode, words, table entry, first word); MODE_GSEED: (mode, words, slot
     # records): guided decoding tables and slot records (_seed_grammar), payload in "input_ids"
@@ -558,9 +592,10 @@ class ModelRunner:
             if g:
                 self._pad_decode(nd, g)
         short = self._short(g, nd)
-        h["header"][:9] = (self.MODE_RUN, T, n, nd, ns, max_q, g, short, 0)
+        lora = self._step_lora if self.lora is not None else 0
+        h["header"][:10] = (self.MODE_RUN, T, n, nd, ns, max_q, g, short, 0, lora)
         self._publish(max(n, g))
-        toks = self._run(T, n, nd, ns, max_q, g, short)
+        toks = self._run(T, n, nd, ns, max_q, g, short, lora)
         return self._handle(toks, ns, want_lp)
 
     def _short(self, g: int, nd: int) -> int:
@@ -661,12 +696,16 @@ class ModelRunner:
             if p.logprobs is not None:
                 h["logprobs"][r] = p.logprobs
                 want_lp = True
+        lora = 0
+        if self.lora is not None:
+            self._fill_lora(seqs, T)
+            lora = self._step_lora
         self._pad_decode(n, g)
         short = self._short(g, n)
-        h["header"][:9] = (self.MODE_RUN, T, n, n, n, 0, g, short, 1)
+        h["header"][:10] = (self.MODE_RUN, T, n, n, n, 0, g, short, 1, lora)
         self._publish(max(n, g))
         self.d["input_ids"][:n].copy_(prev[3][:n])  # step k's sampled ids, stream-ordered
-        return self._handle(self._run(T, n, n, n, 0, g, short), n, want_lp)
+        return self._handle(self._run(T, n, n, n, 0, g, short, lora), n, want_lp)
 
     def _staged_words(self, n_bt_rows: Optional[int]) -> int:
         """int32 words of the staging buffer a step uses: everything up to the used block-table
@@ -745,7 +784,7 @@ class ModelRunner:
                 return
             if nbytes == -3:  # the leader's process is gone (SIGKILL, OOM, crash): end this rank
                 raise TPPeerError("TP leader process died; this worker exits for its supervisor to restart the group")
-            mode, T, n, nd, ns, max_q, g, short, cont = (int(v) for v in self.h["header"][:9])
+            mode, T, n, nd, ns, max_q, g, short, cont, lora = (int(v) for v in self.h["header"][:10])
             if mode == self.MODE_STOP:
                 return
             if mode == self.MODE_SEED:
@@ -764,7 +803,7 @@ class ModelRunner:
             with torch.inference_mode():
                 if cont:
                     self.d["input_ids"][:n].copy_(self._prev_toks[:n])
-                toks = self._run(T, n, nd, ns, max_q, g, short)
+                toks = self._run(T, n, nd, ns, max_q, g, short, lora)
             if toks is not None:
                 self._prev_toks = toks
             self.stats["steps"] += 1
@@ -792,6 +831,8 @@ class ModelRunner:
             self.graph_out.clear()
             self.short_graphs.clear()
             self.short_graph_out.clear()
+            for d in (self.lora_graphs, self.lora_graph_out, self.lora_short_graphs, self.lora_short_graph_out):
+                d.clear()
             self._graph_logits.clear()
             self.graph_pool = None
             self.capture_graphs(sizes)
@@ -820,19 +861,24 @@ class ModelRunner:
             self.channel.publish(self._hnp[self._cur], 64, 60000)
             self.channel.close()
 
-    def _run(self, T: int, n: int, nd: int, ns: int, max_q: int, g: int, short: int = 0):
+    def _run(self, T: int, n: int, nd: int, ns: int, max_q: int, g: int, short: int = 0, lora: int = 0):
         d = self.d
+        if self.lora is not None:
+            self.lora.active = bool(lora)  # the model's LoRA form for this step (eager; graphs hold theirs)
+            self.stats["lora_steps"] += int(bool(lora))
         if g:
+            graphs, outs = ((self.lora_short_graphs, self.lora_short_graph_out) if short else
+                            (self.lora_graphs, self.lora_graph_out)) if lora else \
+                           ((self.short_graphs, self.short_graph_out) if short else (self.graphs, self.graph_out))
+            graphs[g].replay()
+            out = outs[g]
             if short:
-                self.short_graphs[g].replay()
                 self.stats["short_graph_steps"] += 1
-                out = self.short_graph_out[g]
-            else:
-                self.graphs[g].replay()
-                out = self.graph_out[g]
+            if lora:
+                self.stats["lora_graph_steps"] += 1
             self.stats["graph_steps"] += 1
             if self.debug_logits:
-                self.last_logits = self._graph_logits[(g, int(bool(short)))]
+                self.last_logits = self._graph_logits[(g, int(bool(short)) + 2 * int(bool(lora)))]
             return out
         md = self._metadata(nd, n, T, max_q, bool(short))
         hidden = self.model(d["input_ids"][:T], d["positions"][:T], md, self.kv_caches)
@@ -883,6 +929,8 @@ class ModelRunner:
             h["min_p"][nd:g] = 0.0
             h["logprobs"][nd:g] = -1
             h["pen_slot"][nd:g] = -1
+            if self.lora is not None:
+                h["lora_idx"][nd:g] = -1
 
     def default_graph_sizes(self) -> List[int]:
         if self.cfg.graph_batch_sizes:
@@ -908,14 +956,19 @@ class ModelRunner:
         self.h["top_p"][:] = 1.0
         self.h["logprobs"][:] = -1
         self.h["pen_slot"][:] = -1
+        if self.lora is not None:
+            self.h["lora_idx"][:] = -1
         self.h["sample_idx"][: self.cfg.max_num_seqs] = np.arange(self.cfg.max_num_seqs, dtype=np.int32)
         self.dev_buf.copy_(self.host_buf)
         torch.cuda.synchronize(self.device)
         stream = torch.cuda.Stream(self.device)
         variants = (False, True) if self.short_ctx else (False,)
         st = self.model.st
-        for g, short in [(g, v) for g in sorted(sizes, reverse=True) for v in variants]:
+        forms = (False, True) if self.lora is not None else (False,)
+        for g, short, lora in [(g, v, f) for g in sorted(sizes, reverse=True) for v in variants for f in forms]:
             md = self._metadata(g, g, g, 0, short)
+            if self.lora is not None:
+                self.lora.active = lora  # which form of the model this graph records
             if st.dp_attention:  # capture the IPC expert all-to-all path (device-side counts)
                 st.ep_step_rows = g
 
@@ -923,7 +976,7 @@ class ModelRunner:
                 hidden = self.model(d["input_ids"][:g], d["positions"][:g], md, self.kv_caches)
                 logits = self.model.compute_logits(hidden)
                 if self.debug_logits:
-                    self._graph_logits[(g, int(short))] = logits.clone()
+                    self._graph_logits[(g, int(short) + 2 * int(lora))] = logits.clone()
                 return self._sample(logits, g)
 
             # warm up on a side stream (allocator + library handles), then capture
@@ -936,6 +989,12 @@ class ModelRunner:
                 out = run()
             if self.graph_pool is None:
                 self.graph_pool = graph.pool()
-            (self.short_graphs if short else self.graphs)[g] = graph
-            (self.short_graph_out if short else self.graph_out)[g] = out
+            if lora:
+                (self.lora_short_graphs if short else self.lora_graphs)[g] = graph
+                (self.lora_short_graph_out if short else self.lora_graph_out)[g] = out
+            else:
+                (self.short_graphs if short else self.graphs)[g] = graph
+                (self.short_graph_out if short else self.graph_out)[g] = out
+        if self.lora is not None:
+            self.lora.active = False
         torch.cuda.synchronize(self.device)

@@ -63,9 +63,13 @@ class ScheduledBatch:
         return out
 
 
-def _salt(s: Optional[str]) -> int:
-    """Per-request prefix-cache salt (a tenant id): requests only share cached blocks with
-    requests of the same salt.  0 = the shared namespace."""
+def _salt(s: Optional[str], lora: Optional[str] = None) -> int:
+    """Per-request prefix-cache salt, a function of (tenant id, LoRA adapter name): requests only
+    share cached blocks with requests of the same salt -- an adapter changes every k and v, so two
+    adapters (or an adapter and the base model) never share blocks, while the same adapter on the
+    same prompt still does.  0 = the shared namespace (no tenant, no adapter)."""
+    if lora:
+        s = f"{s or ''}\x00lora\x00{lora}"
     if not s:
         return 0
     import hashlib
@@ -173,7 +177,7 @@ class Scheduler:
             return
         bs = self.bm.block_size
         toks = np.asarray(seq.token_slice(0, seq.num_tokens), dtype=np.int32)
-        h = self.bm.prefix_hashes(toks, salt=_salt(seq.cache_salt))
+        h = self.bm.prefix_hashes(toks, salt=_salt(seq.cache_salt, getattr(seq.params, "lora", None)))
         self._hashes[seq.seq_id] = (h, toks)
         usable = max(0, (seq.num_tokens - 2) // bs)  # >= 2 tokens left: the step still samples
         got = self.bm.match_prefix(seq.seq_id, h, toks, min(usable, len(h)))

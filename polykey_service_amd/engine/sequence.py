@@ -58,6 +58,8 @@ class SamplingParams:
     guided_choice: Seq[str] = ()
     guided_json: Optional[str] = None
     guided_suffix: str = ""       # literal text after the guided_json value (a forced tool call's closing)
+    # the LoRA adapter the request runs on (a name from EngineConfig.lora_modules); None = the base model
+    lora: Optional[str] = None
 
     @property
     def has_penalties(self) -> bool:
@@ -111,6 +113,8 @@ class SamplingParams:
             self.guided_json = json.dumps(self.guided_json, sort_keys=True)
         if self.guided_json is not None and not isinstance(self.guided_json, str):
             raise ValueError("guided_json must be a JSON Schema (a dict, or its JSON text)")
+        if self.lora is not None and (not isinstance(self.lora, str) or not self.lora):
+            raise ValueError("lora must be the name of a served adapter")
         if not isinstance(self.guided_suffix, str) or (self.guided_suffix and self.guided_json is None):
             raise ValueError("guided_suffix needs guided_json")
         if (self.guided_regex is not None) + bool(gc) + (self.guided_json is not None) > 1:
@@ -169,6 +173,9 @@ class SamplingParams:
                     v = json.dumps(v, sort_keys=True)
                 elif f.name == "guided_suffix":
                     v = str(v)
+                elif f.name == "lora":
+                    if not isinstance(v, str) or not v:
+                        raise ValueError("lora must be the name of a served adapter")
                 elif f.name == "logprobs":
                     if isinstance(v, bool) or (isinstance(v, float) and v != int(v)):
                         raise ValueError(f"logprobs must be an integer in [0, {MAX_LOGPROBS}]")

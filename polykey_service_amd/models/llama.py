@@ -305,6 +305,8 @@ class LlamaForCausalLM(nn.Module):
         # channel: pack_decode_weights quantises; set before it runs -- README "Weight dtype")
         self.weight_dtype = "bf16"
         self.w8 = False  # the projections are gemm_w8.W8 handles
+        # resident LoRA adapters (models/lora.py LoraState, enable_lora); None: no adapters configured
+        self.lora = None
         self.register_buffer("cos_sin", reference.rope_cos_sin_cache(cfg.max_position, cfg.head_dim, cfg.rope_theta,
                                                                       cfg.rope_scaling, device=self.device),
                              persistent=False)
@@ -440,6 +442,8 @@ class LlamaForCausalLM(nn.Module):
     def forward(self, input_ids: torch.Tensor, positions: torch.Tensor, md: attn_ops.AttnMetadata,
                 kv_caches: List[Tuple[torch.Tensor, torch.Tensor]]) -> torch.Tensor:
         """Returns the final-normed hidden states [T, H]."""
+        if self.lora is not None and self.lora.active:  # a step with at least one adapter row
+            return self._forward_lora(input_ids, positions, md, kv_caches)
         if self._sp_ok(input_ids):
             return self._forward_sp(input_ids, positions, md, kv_caches)
         x = self.embed_tokens(input_ids)
@@ -466,6 +470,113 @@ class LlamaForCausalLM(nn.Module):
         """post-attention residual add + RMSNorm, then the MLP (its output may be pending)."""
         x, residual = add_norm(x, residual, layer.ln2, layer.eps)
         return layer.mlp(x, ws), residual
+
+    # ------------------------------------------------------------------ LoRA
+    def enable_lora(self, adapters, max_rank: int, max_rows: int):
+        """Make ``adapters`` -- (name, :class:`~.lora.LoraAdapter`) pairs -- resident (one slot each)
+        and give the model its LoRA form.  After ``pack_decode_weights``, before the KV cache is
+        sized.  Steps in which no row has an adapter (``self.lora.active`` False) keep today's
+        forward, launch for launch."""
+        from .lora import LoraState
+        if not isinstance(self.layers[0].mlp, LlamaMLP):
+            raise ValueError("LoRA adapters do not support MoE models yet: the expert projections have no "
+                             "adapter path (a follow-up)")
+        if self.st.tp_size > 1 or self.st.ep_size > 1:
+            raise ValueError(f"LoRA adapters do not support tp={self.st.tp_size} / ep={self.st.ep_size} yet: "
+                             "adapters are not sharded (a follow-up)")
+        if self.w8 or self.weight_dtype == "fp8":
+            raise ValueError("LoRA adapters do not support weight_dtype=fp8 yet (a follow-up; use weight_dtype=bf16)")
+        if getattr(self, "packed_only", False):
+            raise ValueError("LoRA adapters need the row-major projection weights next to the block-packed "
+                             "ones (POLYKEY_PACKED_WEIGHTS=packed keeps only the packed copies)")
+        gu = self.layers[0].mlp.gate_up
+        N2, K = gu.shape
+        gu_elems = 0
+        if self.layers[0].attn.qkv_pf is not None:  # the folded chain: slabs of its K-split gate_up
+            gu_elems = max(self._lora_gu_split(N2, K, M) * M for M in range(1, gemm.DECODE_MAX_M + 1)) * N2
+        self.lora = LoraState(self.cfg, adapters, max_rank, max_rows, self.device, gu_elems, self.dtype)
+        return self.lora
+
+    @staticmethod
+    def _lora_gu_split(N2: int, K: int, M: int) -> int:
+        """K split of the LoRA-form chain's gate_up: at least 2, so that its result is a
+        :class:`gemm.Partial` the SiLU slab reduce consumes (the same two launches the split
+        gate_up of the base chain uses)."""
+        return max(2, gemm.gate_up_split(N2, K, M))
+
+    def _forward_lora(self, input_ids: torch.Tensor, positions: torch.Tensor, md: attn_ops.AttnMetadata,
+                      kv_caches: List[Tuple[torch.Tensor, torch.Tensor]]) -> torch.Tensor:
+        """The LoRA form of :meth:`forward` (TP = 1, dense, bf16 weights): the same routing between
+        the folded decode chain and the general path, every projection followed by shrink -> expand
+        of the rows that carry an adapter (``self.lora.idx``, one int32 per token row, -1 = none)."""
+        lora = self.lora
+        x = self.embed_tokens(input_ids)
+        T = x.shape[0]
+        ws = self.workspace(T)
+        writers = not kv_caches or attn_ops.slab_writers_ok(kv_caches[0][0])
+        if (ws is not None and lora.ws_gu is not None and self._rowscale_ok(x)
+                and (md.num_prefill == 0 or (T <= gemm.SKINNY_MAX_M and writers))):
+            return self._forward_rowscale_lora(x, positions, md, kv_caches, ws)
+        # general path: bf16 projections, the delta added in the bf16 form; gate_up un-fused
+        residual = None
+        for i, layer in enumerate(self.layers):
+            at, mlp = layer.attn, layer.mlp
+            if residual is None:
+                residual = x
+                x = ops.rms_norm(x, layer.ln1, layer.eps)
+            else:
+                x, residual = ops.fused_add_rms_norm(x, residual, layer.ln1, layer.eps)
+            qkv = lora.add_bf16(x, gemm.linear(x, at.qkv, packed=at.qkv_p), i, "qkv")
+            a = at.drop(at.attend(qkv, positions, md, self.cos_sin, kv_caches[i]))
+            o = lora.add_bf16(a, gemm.linear(a, at.o, packed=at.o_p), i, "o")
+            x, residual = ops.fused_add_rms_norm(o, residual, layer.ln2, layer.eps)
+            gu = lora.add_bf16(x, gemm.linear(x, mlp.gate_up, packed=mlp.gate_up_p), i, "gate_up")
+            h = gemm.silu_and_mul_interleaved(gu)
+            x = lora.add_bf16(h, gemm.linear(h, mlp.down, packed=mlp.down_p), i, "down")
+        x, _ = ops.fused_add_rms_norm(x, residual, self.norm, self.cfg.rms_eps)
+        return x
+
+    def _forward_rowscale_lora(self, x: torch.Tensor, positions: torch.Tensor, md: attn_ops.AttnMetadata,
+                               kv_caches: List[Tuple[torch.Tensor, torch.Tensor]], ws: torch.Tensor) -> torch.Tensor:
+        """The folded-norm decode chain (:meth:`_forward_rowscale`) in its two-launch forms, each of
+        the four projections' split-K slabs getting its delta (slab form) between the GEMM and the
+        consumer that sums the slabs.  The shrink reads the normalised hidden state
+        (``gemm.norm_apply`` with the layer's norm weight and the chain's parts) and the plain A."""
+        lora = self.lora
+        T, H = x.shape
+        if getattr(self, "_parts_buf", None) is None:
+            self._parts_buf = torch.zeros((H // 64) * gemm.DECODE_MAX_M, dtype=torch.float32, device=self.device)
+            self._parts_buf2 = torch.zeros_like(self._parts_buf)
+        buf, buf2 = self._parts_buf, self._parts_buf2
+        residual = x
+        pending = None
+        half = gemm.QKV_HALF and T <= gemm.SKINNY_MAX_M
+        for i, layer in enumerate(self.layers):
+            at, mlp = layer.attn, layer.mlp
+            kc, vc = kv_caches[i]
+            parts = gemm.residual_parts(pending, residual, buf)
+            xn = gemm.norm_apply(residual, parts, getattr(layer, "ln1_folded", layer.ln1), layer.eps)
+            p = gemm.linear_partial_rowscale(residual, at.qkv, ws, gemm.RowScale(parts, layer.eps),
+                                             packed=at.qkv_pf, half=half)
+            lora.add_slab(xn, p, i, "qkv")  # before RoPE, as it must
+            if md.num_prefill == 0:
+                a = attn_ops.paged_decode_from_qkv(p, positions, self.cos_sin, kc, vc, md, at.scale, at.nq, at.nkv,
+                                                   k_scale=at.k_scale, v_scale=at.v_scale)
+            else:
+                q = gemm.qkv_reduce_rope_cache(p, positions, self.cos_sin, kc, vc, md.slot_mapping, at.nq, at.nkv)
+                a = attn_ops.paged_attention(q, kc, vc, md, at.scale)
+            a = at.drop(a)
+            o = lora.add_slab(a, gemm.linear_partial(a, at.o, ws, packed=at.o_p, half=True), i, "o")
+            parts = gemm.residual_parts(o, residual, buf2)
+            xn = gemm.norm_apply(residual, parts, getattr(layer, "ln2_folded", layer.ln2), layer.eps)
+            N2 = mlp.gate_up.shape[0]
+            gu = gemm.linear_partial_rowscale(residual, mlp.gate_up, lora.ws_gu, gemm.RowScale(parts, layer.eps),
+                                              S=self._lora_gu_split(N2, H, T), packed=mlp.gate_up_pf)
+            lora.add_slab(xn, gu, i, "gate_up")
+            h = gemm.silu_reduce(gu, torch.empty((T, N2 // 2), dtype=residual.dtype, device=residual.device))
+            pending = lora.add_slab(h, gemm.linear_down(h, mlp.down, ws, mlp.down_p), i, "down")
+        x, _ = gemm.partial_add_rms_norm(pending, residual, self.norm, self.cfg.rms_eps)
+        return x
 
     # ------------------------------------------------------------------ sequence parallel (TP prefill)
     def _sp_ok(self, ids: torch.Tensor) -> bool:

@@ -598,3 +598,57 @@ def grammar_advance(pool, rec, slots, tokens, n: int, off, data, V: int, mutant=
             if state >= S:
                 state = -1
         rec[slot, 1] = state
+
+
+# ------------------------------------------------------------------------------ LoRA
+def lora_col_segments(N: int, b0: int, b1: int, il: int, device=None) -> torch.Tensor:
+    """Rank block of every output column of a fused projection (csrc/kernels/lora.hip seg(n)):
+    ``il > 0``: gate / up columns interleaved by ``il``; else the q | k | v boundaries b0 <= b1."""
+    n = torch.arange(N, device=device)
+    if il > 0:
+        return (n // il) & 1
+    return (n >= b0).long() + (n >= b1).long()
+
+
+def lora_shrink(x: torch.Tensor, A: torch.Tensor, idx: torch.Tensor, parts: Optional[torch.Tensor] = None,
+                eps: float = 0.0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """t [M, R] = round(rinv[m] * x[m] @ A[idx[m]]^T) with fp32 products and sums and ONE rounding,
+    to the activation dtype (``out``'s: bf16 wherever the GPU kernels run, float32 in a float32 model);
+    ``A`` [slots, R, K] (zero-padded ranks), ``parts`` [nparts, M] sums of squares of the rows
+    (rinv = 1 / sqrt(sum / K + eps)) or None.  Rows with an index outside [0, slots) are neither
+    read nor written (``out`` keeps them; a fresh ``out`` holds zeros there)."""
+    M, K = x.shape
+    S, R, _ = A.shape
+    if out is None:
+        out = torch.zeros((M, R), dtype=torch.bfloat16, device=x.device)
+    idx = idx[:M].long()
+    for s in range(S):
+        rows = (idx == s).nonzero().flatten()
+        if rows.numel() == 0:
+            continue
+        t = x[rows].float() @ A[s].float().t()
+        if parts is not None:
+            ss = parts[:, :M].float().sum(0)[rows]
+            t = t * (1.0 / torch.sqrt(ss / K + eps))[:, None]
+        out[rows] = t.to(out.dtype)
+    return out
+
+
+def lora_expand(out: torch.Tensor, t: torch.Tensor, B: torch.Tensor, scale: torch.Tensor, idx: torch.Tensor,
+                b0: int, b1: int, il: int) -> torch.Tensor:
+    """out[m, n] += scale[idx[m]] * sum_j B[idx[m]][n, j] * t[m, seg(n) * seg_r + j], in place;
+    ``B`` [slots, N, seg_r], fp32 products and sums, the scale applied last.  fp32 ``out`` (a
+    split-K slab) is added to in fp32; bf16 ``out`` becomes bf16(float(out) + delta)."""
+    M, N = out.shape
+    S, _, seg_r = B.shape
+    seg = lora_col_segments(N, b0, b1, il, out.device)
+    cols = seg[:, None] * seg_r + torch.arange(seg_r, device=out.device)[None, :]  # [N, seg_r] into t's row
+    idx = idx[:M].long()
+    for s in range(S):
+        rows = (idx == s).nonzero().flatten()
+        if rows.numel() == 0:
+            continue
+        tt = t[rows].float()[:, cols]  # [rows, N, seg_r]
+        delta = (tt * B[s].float()[None]).sum(-1) * scale[s].float()
+        out[rows] = (out[rows].float() + delta).to(out.dtype)
+    return out

@@ -38,6 +38,8 @@ class Metrics:
                                         "on this rank (all layers, K and V): halves with an FP8 cache", registry=r)
         self.weight_bytes = Gauge("polykey_engine_weight_bytes", "bytes of the decoder layers' projection weights "
                                   "on this rank: halves with weight_dtype=fp8", registry=r)
+        self.lora_bytes = Gauge("polykey_engine_lora_bytes", "bytes of the resident LoRA adapters: slots x max rank "
+                                "x sum over projections of (K + N) x 2 x layers; 0 without adapters", registry=r)
         self.step_seconds = Histogram("polykey_engine_step_seconds", "engine step wall time", buckets=_TOK_BUCKETS,
                                       registry=r)
         # cumulative engine counts exported as Counters (advanced by the delta since the last step)
@@ -83,6 +85,7 @@ class Metrics:
         self.kv_util.set(1.0 - bm.num_free / max(bm.num_blocks, 1))
         self.kv_bytes_per_token.set(getattr(engine, "kv_bytes_per_token", 0))
         self.weight_bytes.set(getattr(engine, "weight_bytes", 0))
+        self.lora_bytes.set(getattr(engine, "lora_bytes", 0))
         self._advance(self.preemptions, "preemptions", sch.num_preemptions)
         self._advance(self.cached_tokens, "tokens", getattr(sch, "num_cached_tokens", 0))
         self._advance(self.prefix_queries, "queries", getattr(bm, "prefix_queries", 0))
