@@ -436,21 +436,11 @@ int dispatch(const GemmArgs& args, int mode, hipStream_t stream) {
   if (grouped && (a.groups <= 0 || a.max_group_rows <= 0 || a.max_group_rows > kMaxRows || (mode & 7) > kSiluMul ||
                   (mode & 32)))
     return -1;
-  // a group (dense: the whole M) above 64 rows: row tiles of 128 (64 when the row scale has more
-  // than 16 parts per row) for the modes without an in-launch split-K reduction (its per-n-block
-  // tickets would be shared by the row tiles) and without the A-staging norm prologue
-  const int rows = grouped ? a.max_group_rows : a.M;
-  // (bit 8: 64-row tiles regardless -- tools/bench_gemm_rows.py compares the two)
-  a.tile_rows = rows > 64 && !(a.row_scale && a.nrm_nparts > 16) && !(mode & 256) ? 128 : 64;
-  a.row_tiles = (rows + a.tile_rows - 1) / a.tile_rows;
-  if (rows > 64 && (rows > kMaxRows || (mode & 7) > kSiluMul || (mode & 32))) return -1;
-  if (a.N % 128 || a.S < 1 || a.K % (kKC * a.S) || a.lda % 8) return -1;
+  SkinnyTiling tiling;  // row tiles, shape checks, bits 6 and 7
+  if (!skinny_tiling(a, grouped ? a.max_group_rows : a.M, mode, tiling)) return -1;
   const bool packed = (mode & 16) != 0;  // bit 4: W in block-packed layout
   const bool norm = (mode & 32) != 0;    // bit 5: RMSNorm prologue on A
-  // bit 6: non-temporal weight loads (hint); not with several row tiles, whose workgroups of one
-  // W tile read it through the XCD's L2 one after another
-  const bool nt = (mode & 64) != 0 && a.row_tiles == 1;
-  const bool half = (mode & 128) != 0;   // bit 7: 64-row n-blocks (KR = 1)
+  const bool nt = tiling.nt, half = tiling.half;
   if (norm && (a.nrm_parts == nullptr || a.nrm_w == nullptr)) return -1;
   if (half) {  // split-K projections (fp32 slabs, the in-launch residual update); bf16 out with too
                // few 128-row n-blocks to fill the chip (the 70B TP=8 LM-head shard: 126)
@@ -463,8 +453,7 @@ int dispatch(const GemmArgs& args, int mode, hipStream_t stream) {
     }
     if (nt) return -1;
     if (a.row_scale) {  // folded-norm QKV slabs (packed W only)
-      if ((mode & 7) != kPartial || !packed || a.nrm_parts == nullptr || a.nrm_nparts < 1 || a.nrm_nparts > 64)
-        return -1;
+      if ((mode & 7) != kPartial || !packed) return -1;
       return launch<kPartial, true, false, false, true, 1>(a, stream);
     }
     if ((mode & 7) == kPartial)
@@ -482,8 +471,7 @@ int dispatch(const GemmArgs& args, int mode, hipStream_t stream) {
     }
     return -1;
   }
-  if (a.row_scale && (grouped || norm || a.nrm_parts == nullptr || a.nrm_nparts < 1 || a.nrm_nparts > 64))
-    return -1;
+  if (a.row_scale && (grouped || norm)) return -1;
   switch (mode & 7) {
     case kBF16:
       if (a.S != 1 || norm) return -1;

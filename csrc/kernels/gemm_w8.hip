@@ -1,22 +1,25 @@
 // Weight-only FP8 (OCP e4m3, one fp32 scale per output channel) projections.
 //
-//   pk_w8_gemm     the decode GEMM on block-packed e4m3 weights (skinny_tile_w8.h): half the weight
-//                  bytes of the bf16 kernel, the same bf16 MFMA pipeline, the same three epilogues
+//   pk_w8_gemm     the decode GEMM on block-packed e4m3 weights: the W8 instantiations of the one
+//                  decode tile (skinny_tile.h skinny_tile, WFormat<true>) -- half the weight bytes
+//                  of the bf16 kernels, the same bf16 MFMA pipeline, the same three epilogues
 //   pk_w8_widen    packed bytes -> row-major bf16 [N, K] scratch (exact, no scale)   } the prefill
 //   pk_col_scale   out[m, n] = bf16(float(out[m, n]) * scale[n]), in place           } path
 //
 // Prefill-sized M widens a projection into one shared scratch, runs the library GEMM on it and
 // scales the columns (ops/gemm_w8.py).
-#include "skinny_tile_w8.h"
+#include "skinny_tile.h"
 
 using namespace pk;
 
 namespace {
 
+// Instantiated for what the unfused TP=1 decode chain and the general path launch: kBF16 / kPartial /
+// kSiluMul on packed weights, no norm prologue, no in-launch hand-off, not grouped.
 template <int MT, int MODE, bool NT, bool RS, int KR>
 __global__ void __launch_bounds__(256, 2) w8_gemm_kernel(const GemmW8Args args) {
   __shared__ SkinnyLds<MT> lds;
-  skinny_tile_w8<MT, MODE, NT, RS, KR>(args, blockIdx.x, gridDim.x, lds);
+  skinny_tile<MT, MODE, true, false, NT, RS, KR, 0, true>(args, blockIdx.x, 0, gridDim.x, lds, Flow{});
 }
 
 template <int MODE, bool NT, bool RS, int KR = 2>
@@ -36,19 +39,16 @@ int launch_w8(const GemmW8Args& a, hipStream_t stream) {
   return PK_CHECK_LAUNCH();
 }
 
-// the tiling rules of gemm_skinny.hip dispatch, for the modes instantiated here
+// the instantiation switch of the W8 kernels (tiling rules: skinny_tile.h skinny_tiling)
 int dispatch_w8(const GemmW8Args& args, int mode, hipStream_t stream) {
   if (args.M <= 0) return 0;
   GemmW8Args a = args;
-  const bool rs = a.nrm_parts != nullptr;
-  if (a.M > kMaxRows || (mode & ~(7 | 64 | 128)) || (mode & 7) > kSiluMul) return -1;
-  if (a.W == nullptr || a.A == nullptr || a.scale == nullptr) return -1;
-  a.tile_rows = a.M > 64 && !(rs && a.nrm_nparts > 16) ? 128 : 64;
-  a.row_tiles = (a.M + a.tile_rows - 1) / a.tile_rows;
-  if (a.N % 128 || a.S < 1 || a.K % (kKC * a.S) || a.lda % 8) return -1;
-  if (rs && (a.nrm_nparts < 1 || a.nrm_nparts > 64)) return -1;
-  const bool nt = (mode & 64) != 0 && a.row_tiles == 1;  // bit 6: non-temporal weight loads
-  const bool half = (mode & 128) != 0;                   // bit 7: 64-row n-blocks (KR = 1)
+  const bool rs = a.row_scale != 0;
+  if ((mode & ~(7 | 64 | 128)) || (mode & 7) > kSiluMul) return -1;
+  if (a.W == nullptr || a.A == nullptr || a.w_scale == nullptr) return -1;
+  SkinnyTiling tiling;
+  if (!skinny_tiling(a, a.M, mode, tiling)) return -1;
+  const bool nt = tiling.nt, half = tiling.half;
   const int m = mode & 7;
   if (m == kPartial ? a.partial == nullptr : (a.out == nullptr || a.S != 1)) return -1;
   if (half) {  // the split-K slab projections only
@@ -118,10 +118,11 @@ PK_EXPORT int pk_w8_gemm(void* out, void* partial, const void* A, const void* W,
   a.out = static_cast<bf16_t*>(out);
   a.partial = static_cast<float*>(partial);
   a.A = static_cast<const bf16_t*>(A);
-  a.W = static_cast<const fp8_t*>(W);
-  a.scale = static_cast<const float*>(scale);
+  a.W = static_cast<const bf16_t*>(W);  // packed e4m3 bytes: the tile reads them as fp8_t
+  a.w_scale = static_cast<const float*>(scale);
   a.M = M; a.N = N; a.K = K; a.lda = lda; a.ldo = ldo; a.S = S;
   a.nrm_parts = static_cast<const float*>(nrm_parts);
+  a.row_scale = nrm_parts != nullptr;
   a.nrm_nparts = nrm_nparts;
   a.eps = eps;
   return dispatch_w8(a, mode, stream);

@@ -1,11 +1,13 @@
-// The decode GEMM workgroup body (skinny_tile) and its argument block, shared by the plain
-// decode GEMM kernels (gemm_skinny.hip) and the fused decode launches (decode_fused.hip).
+// The decode GEMM workgroup body (skinny_tile), its argument blocks and its tiling rules, shared by
+// the plain decode GEMM kernels (gemm_skinny.hip), the FP8-weight ones (gemm_w8.hip) and the fused
+// decode launches (decode_fused.hip, car_gemm.hip).
 #pragma once
 #include <type_traits>
 
 #include "comm/signals.h"
 #include "common.h"
 #include "flow.h"
+#include "kv_fp8.h"
 
 using namespace pk;
 
@@ -44,6 +46,14 @@ struct GemmArgs {
   int push_rank, push_world; // kPush: this rank, TP group size
 };
 
+// FP8 (OCP e4m3) weights with one fp32 scale per output channel (W8, gemm_w8.hip):
+//   y[m, n] = (sum_k x[m, k] * widen(byte[n, k])) * w_scale[n]      (fp32 products and sums)
+// W holds the block-packed bytes.  (A derived block: GemmArgs is mirrored by ctypes and passed by
+// value ahead of other kernel arguments, so it keeps its layout.)
+struct GemmW8Args : GemmArgs {
+  const float* w_scale;  // [N]
+};
+
 namespace {
 
 
@@ -79,6 +89,43 @@ __device__ __forceinline__ bf16x8_t ldw(const bf16_t* p) {
   if constexpr (NT) return __builtin_nontemporal_load(reinterpret_cast<const bf16x8_t*>(p));
   return *reinterpret_cast<const bf16x8_t*>(p);
 }
+template <bool NT>
+__device__ __forceinline__ u32x4 ldw8(const fp8_t* p) {
+  if constexpr (NT) return __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(p));
+  return *reinterpret_cast<const u32x4*>(p);
+}
+
+// What the tile knows about a weight format: a lane's 16-byte loads of one 16-row tile and 128-deep
+// k-step (kLoads of them, kStride elements apart in the packed layout, a lane's own at kLane * lane)
+// and the MFMA A fragment of k-block s (of 4) of that step.
+//   bf16: four loads, each one fragment.
+//   W8 (ops/gemm_w8.py pack_w8): per (128-row n-block, 128-deep k-step) the 16 KiB a workgroup
+//   consumes are contiguous, as 8 row tiles x 2 loads of 1 KiB in lane order; lane l = 16 g + r of
+//   load jj holds row r, bytes 0-7 = k 32 (2 jj) + 8 g .. + 7 and bytes 8-15 = k 32 (2 jj + 1) +
+//   8 g .. + 7: the fragments of k-blocks 2 jj and 2 jj + 1, raw e4m3.  Activations stay bf16 and
+//   the MFMA is the bf16 one: a half is widened e4m3 -> bf16 (exact, kv_fp8.h fp8_widen8) right
+//   before the MFMAs that consume it.
+template <bool W8>
+struct WFormat {
+  using elem = bf16_t;
+  using raw = bf16x8_t;
+  static constexpr int kLoads = 4, kStride = 512, kLane = 8;
+  template <bool NT>
+  static __device__ __forceinline__ raw load(const elem* p) { return ldw<NT>(p); }
+  static __device__ __forceinline__ bf16x8_t frag(const raw (&f)[kLoads], int s) { return f[s]; }
+};
+template <>
+struct WFormat<true> {
+  using elem = fp8_t;
+  using raw = u32x4;
+  static constexpr int kLoads = 2, kStride = 1024, kLane = 16;
+  template <bool NT>
+  static __device__ __forceinline__ raw load(const elem* p) { return ldw8<NT>(p); }
+  static __device__ __forceinline__ bf16x8_t frag(const raw (&f)[kLoads], int s) {
+    const u32x4 v = f[s >> 1];
+    return __builtin_bit_cast(bf16x8_t, fp8_widen8((s & 1) ? uint2{v[2], v[3]} : uint2{v[0], v[1]}));
+  }
+};
 
 __device__ __forceinline__ float silu(float x) { return x / (1.f + __expf(-x)); }
 
@@ -305,9 +352,17 @@ struct SkinnyLds {
 //      waits for every group its K range overlaps after requesting its first weight k-steps, and
 //      for ALL groups (`fw`, one counter) before the row scale, whose norm parts the collective
 //      writes too -- A and the parts read with sc1 loads
-template <int MT, int MODE, bool PK, bool NORM, bool NT, bool RS = false, int KR = 2, int FL = 0>
-__device__ __forceinline__ void skinny_tile(const GemmArgs& args, const int bx_in, const int by, const int gdx,
+// W8: FP8 weights (Args = GemmW8Args, WFormat<true>).  The format branches below are marked "W8:";
+// everything else -- row tiles, row-scale parts, A staging, both schedules, the epilogues -- is
+// written once for both formats.
+template <int MT, int MODE, bool PK, bool NORM, bool NT, bool RS = false, int KR = 2, int FL = 0, bool W8 = false,
+          class Args = GemmArgs>
+__device__ __forceinline__ void skinny_tile(const Args& args, const int bx_in, const int by, const int gdx,
                                             SkinnyLds<MT>& L, const Flow& fl, const Flow& fw = Flow{}) {
+  static_assert(!W8 || (PK && !NORM), "W8: block-packed weights, no norm prologue");
+  using WF = WFormat<W8>;
+  using wel_t = typename WF::elem;
+  constexpr int kWTile = WF::kLoads * WF::kStride;  // packed elements of one 16-row tile's k-step
   constexpr bool kProd = (FL & 1) != 0;
   constexpr bool kWaitCar = (FL & 4) != 0;
   constexpr bool kWait = (FL & 2) != 0 || kWaitCar;
@@ -318,10 +373,12 @@ __device__ __forceinline__ void skinny_tile(const GemmArgs& args, const int bx_i
   auto& rinv_s = L.rinv;
   int& last_s = L.last;
   const int N = args.N, K = args.K, S = args.S;
-  // rows of this workgroup's group: all rows, or (grouped) expert by's
+  // rows of this workgroup's group: all rows, or (grouped; bf16 only: the W8 kernels do not test
+  // for it, a dependent kernarg load ahead of everything else) expert by's
+  constexpr bool kMayGroup = !W8;
   int gbeg = 0, gend = args.M;
-  const bf16_t* Wg = args.W;
-  if (args.row_offsets != nullptr) {
+  const wel_t* Wg = reinterpret_cast<const wel_t*>(args.W);
+  if (kMayGroup && args.row_offsets != nullptr) {
     gbeg = args.row_offsets[by];
     gend = args.row_offsets[by + 1];
     Wg += static_cast<int64_t>(by) * args.w_stride;
@@ -345,7 +402,8 @@ __device__ __forceinline__ void skinny_tile(const GemmArgs& args, const int bx_i
   const int row0 = gbeg + rt * 16 * MT;
   const int M = min(gend - row0, 16 * MT);
   if (M <= 0) return;  // no tokens routed to this expert (or this row tile): its weights are never read
-  const bf16_t* __restrict__ A = args.a_rows != nullptr ? args.A : args.A + static_cast<int64_t>(row0) * args.lda;
+  const bf16_t* __restrict__ A =
+      kMayGroup && args.a_rows != nullptr ? args.A : args.A + static_cast<int64_t>(row0) * args.lda;
   const int tid = threadIdx.x;
   const int lane = tid & 63, w = tid >> 6;
   const int nb = bx / S, split = bx % S;
@@ -376,7 +434,10 @@ __device__ __forceinline__ void skinny_tile(const GemmArgs& args, const int bx_i
       const int rr = min(64 * h + (tid >> 2), M - 1);
 #pragma unroll
       for (int q = 0; q < kRsLoads; ++q) {
-        const float* p = args.nrm_parts + min(sub + 4 * q, np - 1) * args.M + row0 + rr;
+        // W8: one 32-bit index (<= 64 parts x 1024 rows), as for the A staging below: the address
+        // code is what the W8 kernels were measured with, and it shifts their loop schedule
+        const float* p = W8 ? args.nrm_parts + (min(sub + 4 * q, np - 1) * args.M + row0 + rr)
+                            : args.nrm_parts + min(sub + 4 * q, np - 1) * args.M + row0 + rr;
         rs_p[h * kRsLoads + q] = kWaitCar ? ldf_sc1(args.nrm_parts, p) : *p;  // (parts written in-launch)
       }
     }
@@ -392,23 +453,45 @@ __device__ __forceinline__ void skinny_tile(const GemmArgs& args, const int bx_i
     }
   };
 
-  const bf16_t* wp[kR];
+  // W8: the scales of this lane's 4 output columns per 16-column tile, consumed after the main loop
+  float4 sc_n[W8 ? kR : 1];
+  if constexpr (W8) {
+#pragma unroll
+    for (int t = 0; t < kR; ++t) sc_n[t] = ld4f(args.w_scale + n0 + 16 * t + 4 * g);
+  }
+
+  const wel_t* wp[kR];
 #pragma unroll
   for (int t = 0; t < kR; ++t)
-    wp[t] = PK ? Wg + static_cast<int64_t>(n0 >> 7) * 128 * K + (((n0 & 127) >> 4) + t) * 4 * 512 + 8 * lane  // block-packed
+    wp[t] = PK ? Wg + static_cast<int64_t>(n0 >> 7) * 128 * K + (((n0 & 127) >> 4) + t) * kWTile + WF::kLane * lane  // block-packed
                : Wg + static_cast<int64_t>(n0 + 16 * t + r) * K + 8 * g;                     // row-major [N, K]
 
   // A staging: MT*16 rows x kKA cols of 16-byte pieces over 256 threads
   constexpr int kPieces = (16 * MT * kPPR + 255) / 256;
   u32x4 stage[kPieces];
   u32x4 stage_w[NORM ? kPieces : 1];
-  const bf16_t* arow[kPieces];  // source row of each staged piece (fixed across k-chunks)
+  // Source of each staged piece (fixed across k-chunks): its row's pointer.
+  // W8: a 32-bit element offset from A instead, holding row and column (rows <= 1024).  With row
+  // pointers every MT = 8 W8 kernel needs 8 to 12 more VGPRs, and the slabs / row-scale / 128-row
+  // n-block one (folded QKV above 64 rows) reaches 256 and spills in the loop.  (The bf16 tile would
+  // probably gain the same registers: not measured.)
+  std::conditional_t<W8, int, const bf16_t*> asrc[kPieces];
 #pragma unroll
   for (int p = 0; p < kPieces; ++p) {
     const int src_row = min((tid + 256 * p) / kPPR, M - 1);
-    const int r_a = args.a_rows != nullptr ? args.a_rows[row0 + src_row] / args.a_row_div : src_row;
-    arow[p] = A + static_cast<int64_t>(r_a) * args.lda;
+    if constexpr (W8) {  // (not grouped: no a_rows)
+      asrc[p] = src_row * args.lda + ((tid + 256 * p) % kPPR) * 8;
+    } else {
+      const int r_a = args.a_rows != nullptr ? args.a_rows[row0 + src_row] / args.a_row_div : src_row;
+      asrc[p] = A + static_cast<int64_t>(r_a) * args.lda;
+    }
   }
+  auto a_src = [&](int p, int kc, int col) -> const bf16_t* {
+    if constexpr (W8)
+      return A + kc + asrc[p];
+    else
+      return asrc[p] + kc + col;
+  };
   auto load_a = [&](int kc) {
 #pragma unroll
     for (int p = 0; p < kPieces; ++p) {
@@ -416,9 +499,9 @@ __device__ __forceinline__ void skinny_tile(const GemmArgs& args, const int bx_i
       if constexpr (kWait)  // the producers' output, handed off in-launch: sc1 loads
         stage[p] = __builtin_amdgcn_raw_buffer_load_b128(
             __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(args.A), static_cast<short>(0), 0x7ffffff0, 0x00020000),
-            static_cast<int>((arow[p] + kc + col - args.A) * 2), 0, 16);
+            static_cast<int>((a_src(p, kc, col) - args.A) * 2), 0, 16);
       else
-        stage[p] = *reinterpret_cast<const u32x4*>(arow[p] + kc + col);
+        stage[p] = *reinterpret_cast<const u32x4*>(a_src(p, kc, col));
       if constexpr (NORM) stage_w[p] = *reinterpret_cast<const u32x4*>(args.nrm_w + kc + col);
     }
   };
@@ -447,16 +530,18 @@ __device__ __forceinline__ void skinny_tile(const GemmArgs& args, const int bx_i
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt) acc[t][mt] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-  bf16x8_t wa[kR][4], wb[kR][4];
-  auto load_w = [&](bf16x8_t (&dst)[kR][4], int k) {
+  // one 128-deep k-step of weights per buffer, as loaded (W8: raw e4m3, widened at use)
+  using wraw_t = typename WF::raw;
+  wraw_t wa[kR][WF::kLoads], wb[kR][WF::kLoads];
+  auto load_w = [&](wraw_t (&dst)[kR][WF::kLoads], int k) {
 #pragma unroll
     for (int t = 0; t < kR; ++t)
 #pragma unroll
-      for (int s = 0; s < 4; ++s)
-        dst[t][s] = PK ? ldw<NT>(wp[t] + static_cast<int64_t>(k >> 7) * (32 * 512) + s * 512)
-                       : ldw<NT>(wp[t] + k + 32 * s);
+      for (int s = 0; s < WF::kLoads; ++s)
+        dst[t][s] = PK ? WF::template load<NT>(wp[t] + static_cast<int64_t>(k >> 7) * (8 * kWTile) + s * WF::kStride)
+                       : WF::template load<NT>(wp[t] + k + 32 * s);
   };
-  auto mma_step = [&](const bf16x8_t (&wf)[kR][4], int buf, int kk) {
+  auto mma_step = [&](const wraw_t (&wf)[kR][WF::kLoads], int buf, int kk) {
 #pragma unroll
     for (int s = 0; s < 4; ++s) {
       bf16x8_t af[MT];
@@ -464,10 +549,12 @@ __device__ __forceinline__ void skinny_tile(const GemmArgs& args, const int bx_i
       for (int mt = 0; mt < MT; ++mt)
         af[mt] = *reinterpret_cast<const bf16x8_t*>(&a_lds[buf][16 * mt + r][kk + 32 * s + 8 * g]);
 #pragma unroll
-      for (int t = 0; t < kR; ++t)
+      for (int t = 0; t < kR; ++t) {
+        const bf16x8_t wv = WF::frag(wf[t], s);
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt)
-          acc[t][mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[t][s], af[mt], acc[t][mt], 0, 0, 0);
+          acc[t][mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wv, af[mt], acc[t][mt], 0, 0, 0);
+      }
     }
   };
 
@@ -569,6 +656,15 @@ __device__ __forceinline__ void skinny_tile(const GemmArgs& args, const int bx_i
   for (int mt = 0; mt < MT; ++mt) {
     const int m = 16 * mt + r;
     if (m >= M) continue;
+    if constexpr (W8) {  // the channel scale, before the row scale
+#pragma unroll
+      for (int t = 0; t < kR; ++t) {
+        acc[t][mt][0] *= sc_n[t].x;
+        acc[t][mt][1] *= sc_n[t].y;
+        acc[t][mt][2] *= sc_n[t].z;
+        acc[t][mt][3] *= sc_n[t].w;
+      }
+    }
     if constexpr (RS) {  // folded RMSNorm: x W^T = rinv[m] * (residual (W diag(w))^T)
       const float sc = rinv_s[m];
 #pragma unroll
@@ -648,6 +744,30 @@ __device__ __forceinline__ void skinny_tile(const GemmArgs& args, const int bx_i
       default: epilogue<MODE, 0, KR>(args, nb); break;
     }
   }
+}
+
+// The tiling rules of the plain decode GEMM launches, for both weight formats (dispatch in
+// gemm_skinny.hip, dispatch_w8 in gemm_w8.hip).  `rows` is the largest group's row count (dense:
+// M).  Sets a.tile_rows / a.row_tiles and decodes the tiling bits of `mode`; false: a shape that is
+// not tiled.
+struct SkinnyTiling {
+  bool nt;    // bit 6: non-temporal weight loads (hint); not with several row tiles, whose workgroups
+              //   of one W tile read it through the XCD's L2 one after another
+  bool half;  // bit 7: 64-row n-blocks (KR = 1)
+};
+inline bool skinny_tiling(GemmArgs& a, int rows, int mode, SkinnyTiling& t) {
+  // a group (dense: the whole M) above 64 rows: row tiles of 128 (64 when the row scale has more
+  // than 16 parts per row) for the modes without an in-launch split-K reduction (its per-n-block
+  // tickets would be shared by the row tiles) and without the A-staging norm prologue
+  // (bit 8: 64-row tiles regardless -- tools/bench_gemm_rows.py compares the two)
+  a.tile_rows = rows > 64 && !(a.row_scale && a.nrm_nparts > 16) && !(mode & 256) ? 128 : 64;
+  a.row_tiles = (rows + a.tile_rows - 1) / a.tile_rows;
+  if (rows > kMaxRows || (rows > 64 && ((mode & 7) > kSiluMul || (mode & 32)))) return false;
+  if (a.N % 128 || a.S < 1 || a.K % (kKC * a.S) || a.lda % 8) return false;
+  if (a.row_scale && (a.nrm_parts == nullptr || a.nrm_nparts < 1 || a.nrm_nparts > 64)) return false;
+  t.nt = (mode & 64) != 0 && a.row_tiles == 1;
+  t.half = (mode & 128) != 0;
+  return true;
 }
 
 }  // namespace

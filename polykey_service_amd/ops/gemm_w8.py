@@ -3,7 +3,8 @@ one fp32 scale per output channel (row of the ``[N, K]`` weight).
 
 Activations, accumulation and outputs are those of the bf16 projections (:mod:`.gemm`); only the
 weight stream changes.  Up to :data:`KERNEL_MAX_M` rows the hand-written decode GEMM
-(``csrc/kernels/gemm_w8.hip``) streams the block-packed bytes (:func:`pack_w8`) and widens them to
+(``csrc/kernels/gemm_w8.hip``: the W8 instantiations of the bf16 kernels' tile body,
+``skinny_tile.h``) streams the block-packed bytes (:func:`pack_w8`) and widens them to
 bf16 in registers; above it the *wide path* widens the projection into a bf16 scratch,
 runs the library GEMM on it and scales the output columns.  The ops mirror their bf16 namesakes
 and share their tiling rules, so the fp32 slabs feed the same reducers.  CPU tensors take the fp32

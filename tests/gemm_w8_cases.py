@@ -31,10 +31,10 @@ BF16 = torch.bfloat16
 GRID_VALUES = [0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0, 8.0, -0.5, -1.0, -1.5, -2.0, -3.0, -4.0, -6.0, -8.0]
 MUTANTS = ("scale_next", "kblock_swap", "tile_swap", "gate_up_swap", "drop_last_split", "scale_after_round")
 
-# (N, K) of the kernel tests and the row counts: every MT (1, 2, 4), the 128-row MT = 8 variant
-# with one and two row tiles, ragged last tiles
+# (N, K) of the kernel tests and the row counts: every MT (1, 2, 4; 40 rows = three 16-row tiles
+# run the MT = 4 kernel), the 128-row MT = 8 variant with one and two row tiles, ragged last tiles
 SHAPES = [(128, 256), (256, 512), (384, 1024), (768, 512), (1024, 14336)]
-ROWS = [1, 15, 16, 17, 64, 65, 128, 200]
+ROWS = [1, 15, 16, 17, 40, 64, 65, 128, 200]
 
 
 @dataclasses.dataclass
