@@ -1,7 +1,8 @@
 """The W8 (weight-only FP8) kernels on the GPU: the decode GEMM in every instantiated mode against
 the float64 reference (exact grid cases, needles, NaN sentinels), against the bf16 kernel of the
 same build where the epilogue is shared (row scale, SiLU), random values within derived bounds,
-the widen / column-scale kernels, the wide path, and a captured graph.
+the widen / column-scale kernels, the wide path, and a captured graph.  The "equals the bf16 kernel"
+assertions rest on tests/kernels/test_gemm_exact.py, which pins that kernel to float64.
 
 tests/unit/test_gemm_w8_cases.py proves on the CPU that these inputs reject wrong kernels."""
 import functools
