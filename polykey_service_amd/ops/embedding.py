@@ -17,7 +17,7 @@ def embedding(ids: torch.Tensor, table: torch.Tensor, vocab_start: int = 0, voca
         local = ids.long() - vocab_start
         mask = (local >= 0) & (local < vocab_local)
         x = F.embedding(torch.where(mask, local, torch.zeros_like(local)), table)
-        return x * mask.unsqueeze(-1).to(x.dtype)
+        return torch.where(mask.unsqueeze(-1), x, torch.zeros_like(x))  # zeros even where row 0 holds NaN / inf
     ids32 = ids.reshape(-1)
     if ids32.dtype != torch.int32:
         ids32 = ids32.to(torch.int32)
