@@ -91,6 +91,20 @@ __device__ __forceinline__ float wave_max(float v) {
   return v;
 }
 
+// Sum over the aligned group of 8 lanes a lane belongs to (all 8 active), on every lane of it: three
+// DPP adds (quad_perm [1,0,3,2], quad_perm [2,3,0,1], row_half_mirror) on the VALU -- no LDS round
+// trip, unlike __shfl_xor's ds_bpermute.
+__device__ __forceinline__ float group8_sum(float v) {
+  v += __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0xB1, 0xF, 0xF, true));
+  v += __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0x4E, 0xF, 0xF, true));
+  v += __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0x141, 0xF, 0xF, true));
+  return v;
+}
+
+// QK-norm (Qwen3): the per-head RMSNorm scale of a 128-wide q or k head from its sum of squares.
+// One definition, so that every kernel that normalises a head computes the same bits.
+__device__ __forceinline__ float head_rinv(float ss, float eps) { return rsqrtf(ss * (1.f / 128.f) + eps); }
+
 // Block-wide sum for blockDim.x <= 1024 (<= 16 waves). `red` needs 16 floats of LDS.
 __device__ __forceinline__ float block_sum(float v, float* red) {
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, nw = (blockDim.x + 63) >> 6;

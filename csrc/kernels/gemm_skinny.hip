@@ -322,11 +322,21 @@ __global__ void __launch_bounds__(1024) splitk_add_rmsnorm_kernel(bf16_t* __rest
 // cache (slot < 0: padding row, nothing cached).  Replaces reduce + rope_and_cache.
 // One wave per (row, head) so M * (nq + 2 nkv) waves cover the chip and every lane issues its
 // 2 S slab loads back to back (a per-row workgroup walking heads serially was latency-bound).
-template <int SS>
+// QN... is empty, or one QkNormW (pk_qkv_reduce_rope_cache_qknorm, Qwen3): q and k heads are
+// RMS-normalised over their 128 values and scaled by a [128] bf16 weight before the rotation,
+// y = x * rsqrt(sum x^2 / 128 + eps) * w in fp32 (common.h head_rinv); the wave holds one head,
+// so the sum of squares is one wave_sum.  v heads skip it.
+struct QkNormW {
+  const bf16_t* qw;
+  const bf16_t* kw;
+  float eps;
+};
+
+template <int SS, typename... QN>
 __global__ void __launch_bounds__(256) qkv_reduce_rope_cache_kernel(
     bf16_t* __restrict__ q_out, const float* __restrict__ partial, int S, int M, int nq, int nkv,
     const int* __restrict__ positions, const float* __restrict__ cos_sin, bf16_t* __restrict__ kc,
-    bf16_t* __restrict__ vc, const int* __restrict__ slots, int bs) {
+    bf16_t* __restrict__ vc, const int* __restrict__ slots, int bs, QN... qn) {
   const int nh = nq + 2 * nkv;
   const int item = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (item >= M * nh) return;
@@ -363,6 +373,13 @@ __global__ void __launch_bounds__(256) qkv_reduce_rope_cache_kernel(
   if (h < nq + nkv) {
     a = rbf(a);
     b = rbf(b);
+    if constexpr (sizeof...(QN) > 0) {
+      const QkNormW n = (qn, ...);
+      const float rinv = head_rinv(wave_sum(a * a + b * b), n.eps);
+      const bf16_t* w = h < nq ? n.qw : n.kw;
+      a = a * rinv * bf2f(w[lane]);
+      b = b * rinv * bf2f(w[lane + 64]);
+    }
     const float* cs = cos_sin + static_cast<int64_t>(positions[m]) * 128;
     const float co = cs[lane], si = cs[64 + lane];
     if (h < nq) {
@@ -710,6 +727,31 @@ PK_EXPORT int pk_qkv_reduce_rope_cache(void* q_out, const void* partial, int S, 
         static_cast<bf16_t*>(q_out), static_cast<const float*>(partial), S, M, nq, nkv,
         static_cast<const int*>(positions), static_cast<const float*>(cos_sin), static_cast<bf16_t*>(k_cache),
         static_cast<bf16_t*>(v_cache), static_cast<const int*>(slots), bs);
+  };
+  switch (S) {
+    case 2: go(std::integral_constant<int, 2>{}); break;
+    case 4: go(std::integral_constant<int, 4>{}); break;
+    case 8: go(std::integral_constant<int, 8>{}); break;
+    case 16: go(std::integral_constant<int, 16>{}); break;
+    default: go(std::integral_constant<int, 0>{}); break;
+  }
+  return PK_CHECK_LAUNCH();
+}
+
+// pk_qkv_reduce_rope_cache with QK-norm (QkNormW above): q_norm_w / k_norm_w are [128] bf16.
+PK_EXPORT int pk_qkv_reduce_rope_cache_qknorm(void* q_out, const void* partial, int S, int M, int nq, int nkv,
+                                              const void* positions, const void* cos_sin, void* k_cache,
+                                              void* v_cache, const void* slots, int bs, const void* q_norm_w,
+                                              const void* k_norm_w, float eps, hipStream_t stream) {
+  if (M <= 0) return 0;
+  if (bs <= 0 || bs % 32 || S < 1 || q_norm_w == nullptr || k_norm_w == nullptr) return -1;
+  const int grid = (M * (nq + 2 * nkv) + 3) / 4;
+  const QkNormW qn{static_cast<const bf16_t*>(q_norm_w), static_cast<const bf16_t*>(k_norm_w), eps};
+  auto go = [&](auto ss) {
+    qkv_reduce_rope_cache_kernel<decltype(ss)::value><<<grid, 256, 0, stream>>>(
+        static_cast<bf16_t*>(q_out), static_cast<const float*>(partial), S, M, nq, nkv,
+        static_cast<const int*>(positions), static_cast<const float*>(cos_sin), static_cast<bf16_t*>(k_cache),
+        static_cast<bf16_t*>(v_cache), static_cast<const int*>(slots), bs, qn);
   };
   switch (S) {
     case 2: go(std::integral_constant<int, 2>{}); break;

@@ -5,6 +5,8 @@
 // rotated k is also written to the K cache [block][kv_head][slot][128] and v to the
 // transposed V cache [block][kv_head][128][block_size].  One workgroup per 32 tokens (below).
 // slot_mapping[t] < 0 marks a padding row: it is rotated but nothing is cached.
+#include <type_traits>
+
 #include "common.h"
 #include "kv_fp8.h"
 
@@ -29,10 +31,29 @@ constexpr int kHalf = 64;
 // token single bytes.
 constexpr int kTokTile = 32;
 
-__device__ __forceinline__ KvScale only(KvScale s) { return s; }
+// QK-norm (Qwen3, pk_rope_and_cache_qknorm): every q and k head is RMS-normalised over its 128
+// values and scaled by a [128] bf16 weight (qw for q heads, kw for k heads) BEFORE the rotation,
+//     y_i = x_i * rsqrt(sum_j x_j^2 / 128 + eps) * w_i      (fp32, common.h head_rinv)
+// and the rotation of y is rounded to bf16 once.  The 8 lanes that share a head hold 16 values
+// each; the sum of squares is three DPP adds inside that group (common.h group8_sum: nothing goes
+// through LDS).
+struct QkNorm {
+  const bf16_t* qw;
+  const bf16_t* kw;
+  float eps;
+};
+
+template <typename T, typename... A>
+constexpr bool kHas = (std::is_same_v<T, A> || ...);
+
+template <typename T, typename A0, typename... A>
+__device__ __forceinline__ T pick(A0 a0, A... a) {
+  if constexpr (std::is_same_v<T, A0>) return a0;
+  else return pick<T>(a...);
+}
 
 // (SC is a pack so that the bf16 kernel keeps its argument list, and with it its code, unchanged:
-// empty for bf16, one KvScale for FP8)
+// empty for bf16, one KvScale for FP8, then one QkNorm for the QK-norm entry point)
 template <typename CT, typename... SC>
 __global__ void __launch_bounds__(256) rope_and_cache_kernel(bf16_t* __restrict__ qkv, const int* __restrict__ positions,
                                                              const float* __restrict__ cos_sin, CT* __restrict__ kc,
@@ -45,6 +66,17 @@ __global__ void __launch_bounds__(256) rope_and_cache_kernel(bf16_t* __restrict_
   if (threadIdx.x < kTokTile) slot_s[threadIdx.x] = (slots && threadIdx.x < nt) ? slots[t0 + threadIdx.x] : -1;
   __syncthreads();
   const int n_rot = (nq + nkv) * 8;  // 8 lanes x 8 pairs per head
+  // QK-norm weights of this lane's 16 channels, loaded once: n_rot and blockDim.x are multiples of
+  // 8, so (u % n_rot) & 7 is threadIdx.x & 7 on every iteration
+  [[maybe_unused]] u32x4 wq[2], wk[2];
+  if constexpr (kHas<QkNorm, SC...>) {
+    const QkNorm qn = pick<QkNorm>(sc...);
+    const int cw = (threadIdx.x & 7) * 8;
+    wq[0] = *reinterpret_cast<const u32x4*>(qn.qw + cw);
+    wq[1] = *reinterpret_cast<const u32x4*>(qn.qw + cw + kHalf);
+    wk[0] = *reinterpret_cast<const u32x4*>(qn.kw + cw);
+    wk[1] = *reinterpret_cast<const u32x4*>(qn.kw + cw + kHalf);
+  }
   for (int u = threadIdx.x; u < nt * n_rot; u += blockDim.x) {
     const int tt = u / n_rot, item = u % n_rot;
     const int t = t0 + tt;
@@ -60,6 +92,22 @@ __global__ void __launch_bounds__(256) rope_and_cache_kernel(bf16_t* __restrict_
     co[0] = c0.x; co[1] = c0.y; co[2] = c0.z; co[3] = c0.w; co[4] = c1.x; co[5] = c1.y; co[6] = c1.z; co[7] = c1.w;
     si[0] = s0.x; si[1] = s0.y; si[2] = s0.z; si[3] = s0.w; si[4] = s1.x; si[5] = s1.y; si[6] = s1.z; si[7] = s1.w;
     float ra[8], rb[8];
+    if constexpr (kHas<QkNorm, SC...>) {
+      float ss = 0.f;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) ss += a[j] * a[j] + b[j] * b[j];
+      // u is a multiple of 8 at lane 0 of every group and nt * n_rot is one too: a group's 8
+      // lanes are in the loop together
+      const float rinv = head_rinv(group8_sum(ss), pick<QkNorm>(sc...).eps);
+      float wa[8], wb[8];
+      unpack8(head < nq ? wq[0] : wk[0], wa);
+      unpack8(head < nq ? wq[1] : wk[1], wb);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        a[j] = a[j] * rinv * wa[j];
+        b[j] = b[j] * rinv * wb[j];
+      }
+    }
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       ra[j] = a[j] * co[j] - b[j] * si[j];
@@ -73,7 +121,7 @@ __global__ void __launch_bounds__(256) rope_and_cache_kernel(bf16_t* __restrict_
       const int kh = head - nq;
       CT* dst = kc + (static_cast<int64_t>(slot / bs) * nkv + kh) * bs * kHD;  // fragment-native tile
       if constexpr (kIsFp8<CT>) {
-        const float ksc = only(sc...).k;
+        const float ksc = pick<KvScale>(sc...).k;
         unpack8(va, ra);  // the bf16 values just stored
         unpack8(vb, rb);
 #pragma unroll
@@ -105,7 +153,7 @@ __global__ void __launch_bounds__(256) rope_and_cache_kernel(bf16_t* __restrict_
     for (int u = threadIdx.x; u < n_v; u += blockDim.x) {  // u = kv head * 128 + channel
       const int kh = u / kHD, d = u % kHD;
       if constexpr (kIsFp8<CT>) {
-        const float vsc = only(sc...).v;
+        const float vsc = pick<KvScale>(sc...).v;
         CT* vb = vc + (static_cast<int64_t>(blk) * nkv + kh) * kHD * bs;
 #pragma unroll
         for (int q = 0; q < 4; ++q) {  // 8 keys per 8-byte piece, packed in registers
@@ -137,7 +185,7 @@ __global__ void __launch_bounds__(256) rope_and_cache_kernel(bf16_t* __restrict_
     const int kh = e / kHD, d = e % kHD;
     if constexpr (kIsFp8<CT>)
       vc[(static_cast<int64_t>(slot / bs) * nkv + kh) * kHD * bs + vcache_off(slot % bs, d)] =
-          fp8_from(fp8_prep(bf2f(qkv[static_cast<int64_t>(t0 + tt) * q_stride + voff + e]), only(sc...).v));
+          fp8_from(fp8_prep(bf2f(qkv[static_cast<int64_t>(t0 + tt) * q_stride + voff + e]), pick<KvScale>(sc...).v));
     else
       vc[(static_cast<int64_t>(slot / bs) * nkv + kh) * kHD * bs + vcache_off(slot % bs, d)] =
           qkv[static_cast<int64_t>(t0 + tt) * q_stride + voff + e];
@@ -159,6 +207,25 @@ PK_EXPORT int pk_rope_and_cache(void* qkv, const void* positions, const void* co
         static_cast<bf16_t*>(qkv), static_cast<const int*>(positions), static_cast<const float*>(cos_sin),
         static_cast<CT*>(k_cache), static_cast<CT*>(v_cache), static_cast<const int*>(slot_mapping), T, nq, nkv, bs,
         q_stride, sc...);
+    return PK_CHECK_LAUNCH();
+  });
+}
+
+// pk_rope_and_cache with QK-norm (QkNorm above): q_norm_w / k_norm_w are [128] bf16, v is untouched,
+// padding rows (slot < 0) are normalised and rotated but not cached.
+PK_EXPORT int pk_rope_and_cache_qknorm(void* qkv, const void* positions, const void* cos_sin, void* k_cache,
+                                       void* v_cache, const void* slot_mapping, const void* q_norm_w,
+                                       const void* k_norm_w, float eps, int T, int nq, int nkv, int hd, int bs,
+                                       int q_stride, int kv_dtype, float k_scale, float v_scale, hipStream_t stream) {
+  if (T <= 0) return 0;
+  if (hd != kHD || (bs % 32) != 0 || q_norm_w == nullptr || k_norm_w == nullptr) return -1;
+  const QkNorm qn{static_cast<const bf16_t*>(q_norm_w), static_cast<const bf16_t*>(k_norm_w), eps};
+  return with_kv_type(kv_dtype, k_scale, v_scale, [&](auto ct, auto... sc) {
+    using CT = decltype(ct);
+    rope_and_cache_kernel<CT><<<(T + kTokTile - 1) / kTokTile, 256, 0, stream>>>(
+        static_cast<bf16_t*>(qkv), static_cast<const int*>(positions), static_cast<const float*>(cos_sin),
+        static_cast<CT*>(k_cache), static_cast<CT*>(v_cache), static_cast<const int*>(slot_mapping), T, nq, nkv, bs,
+        q_stride, sc..., qn);
     return PK_CHECK_LAUNCH();
   });
 }

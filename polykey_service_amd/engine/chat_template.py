@@ -3,7 +3,7 @@
 The reference only routes by tool name (``/root/reference/internal/service/mock.go:32-64``,
 advertised as "OpenRouter-esque", ``/root/reference/README.md:27``); an on-node model has to
 turn a chat (with optional function tools) into one prompt and its completion back into
-either text or tool calls.  Two families are built in, matching the north-star models:
+either text or tool calls.  Three families are built in, matching the served models:
 
 * ``llama3`` (Llama-3 8B / 70B): header-delimited turns ending in ``<|eot_id|>``; tools are
   described as JSON schemas in the system turn and a call is a JSON object
@@ -12,7 +12,10 @@ either text or tool calls.  Two families are built in, matching the north-star m
 * ``mistral`` (Mixtral-8x7B): ``[INST] ... [/INST]`` turns; tools in
   ``[AVAILABLE_TOOLS] [...] [/AVAILABLE_TOOLS]`` before the last user turn; a call is
   ``[TOOL_CALLS] [{"name": ..., "arguments": {...}}, ...]`` and results are
-  ``[TOOL_RESULTS] {...} [/TOOL_RESULTS]``.
+  ``[TOOL_RESULTS] {...} [/TOOL_RESULTS]``;
+* ``chatml`` (Qwen3): ``<|im_start|>{role}\n{content}<|im_end|>\n`` turns; tools are described in the
+  system turn inside ``<tools></tools>``; a call is ``<tool_call>\n{"name": ..., "arguments": {...}}\n
+  </tool_call>`` and results come back in a user turn as ``<tool_response>...</tool_response>``.
 
 When a local tokenizer directory carries a ``tokenizer_config.json`` with a ``chat_template``,
 that Jinja template is rendered instead (sandboxed: no attribute access to Python internals)
@@ -27,6 +30,7 @@ from typing import Any, Dict, List, Optional
 
 LLAMA3 = "llama3"
 MISTRAL = "mistral"
+CHATML = "chatml"
 
 
 def _content(m: Dict[str, Any]) -> str:
@@ -90,6 +94,8 @@ class ChatTemplate:
             return text
         if self.family == MISTRAL:
             return self._render_mistral(messages, specs)
+        if self.family == CHATML:
+            return self._render_chatml(messages, specs, add_generation_prompt)
         return self._render_llama3(messages, specs, add_generation_prompt)
 
     def _render_llama3(self, messages, specs, add_generation_prompt) -> str:
@@ -153,15 +159,66 @@ class ChatTemplate:
                 parts.append("[TOOL_RESULTS] " + json.dumps(res, ensure_ascii=False) + "[/TOOL_RESULTS]")
         return "".join(parts)
 
+    def _render_chatml(self, messages, specs, add_generation_prompt) -> str:
+        def turn(role: str, body: str) -> str:
+            return f"<|im_start|>{role}\n{body}<|im_end|>\n"
+
+        parts = []
+        msgs = list(messages)
+        system = ""
+        if msgs and msgs[0].get("role") == "system":
+            system = _content(msgs.pop(0))
+        if specs:
+            tool_text = ("# Tools\n\nYou may call one or more functions to assist with the user query.\n\n"
+                         "You are provided with function signatures within <tools></tools> XML tags:\n<tools>\n"
+                         + "\n".join(json.dumps(s, ensure_ascii=False) for s in specs) + "\n</tools>\n\n"
+                         "For each function call, return a json object with function name and arguments within "
+                         "<tool_call></tool_call> XML tags:\n<tool_call>\n"
+                         '{"name": <function-name>, "arguments": <args-json-object>}\n</tool_call>')
+            system = (system + "\n\n" + tool_text) if system else tool_text
+        if system:
+            parts.append(turn("system", system))
+        results: List[str] = []  # consecutive tool results share one user turn
+
+        def flush():
+            if results:
+                parts.append(turn("user", "\n".join(results)))
+                results.clear()
+
+        for m in msgs:
+            role = m.get("role", "user")
+            if role in ("tool", "ipython"):
+                results.append(f"<tool_response>\n{_content(m)}\n</tool_response>")
+                continue
+            flush()
+            if role == "assistant" and m.get("tool_calls"):
+                calls = "\n".join("<tool_call>\n" + json.dumps(
+                    {"name": c.get("function", c).get("name"), "arguments": _call_args(c)}, ensure_ascii=False)
+                    + "\n</tool_call>" for c in m["tool_calls"])
+                body = _content(m)
+                parts.append(turn("assistant", (body + "\n" + calls) if body else calls))
+            else:
+                parts.append(turn(role, _content(m)))
+        flush()
+        if add_generation_prompt:
+            parts.append("<|im_start|>assistant\n")
+        return "".join(parts)
+
     # ------------------------------------------------------------- forced calls
     def call_prefix(self, name: Optional[str]) -> str:
+        if self.family == CHATML:
+            return '<tool_call>\n{"name": "' + (f'{name}", "arguments": ' if name else "")
         if self.family == MISTRAL:
             return '[TOOL_CALLS] [{"name": "' + (f'{name}", "arguments": ' if name else "")
         return '<|python_tag|>{"name": "' + (f'{name}", "parameters": ' if name else "")
 
 
-def family_for(model_name: str, is_moe: bool = False) -> str:
+def family_for(model_name: str, is_moe: bool = False, qk_norm: bool = False) -> str:
+    """The built-in template family of a model: by name, or by structure (``qk_norm``: a Qwen3
+    checkpoint directory whose name does not say so)."""
     n = (model_name or "").lower()
+    if "qwen" in n or (qk_norm and not is_moe):
+        return CHATML
     return MISTRAL if is_moe or "mixtral" in n or "mistral" in n else LLAMA3
 
 
@@ -177,7 +234,7 @@ def load_chat_template(tokenizer_dir: str, family: str) -> ChatTemplate:
             src = next((t.get("template") for t in src if t.get("name") == "default"), None)
         if isinstance(src, str) and src:
             fam = MISTRAL if "[TOOL_CALLS]" in src or "[INST]" in src else (
-                LLAMA3 if "<|start_header_id|>" in src else family)
+                LLAMA3 if "<|start_header_id|>" in src else (CHATML if "<|im_start|>" in src else family))
             eos = tc.get("eos_token")
             eos = eos.get("content") if isinstance(eos, dict) else eos
             return ChatTemplate(fam, jinja_source=src, special={"eos_token": eos or ""})

@@ -90,7 +90,7 @@ def tokenizer_for(cfg: EngineConfig, mcfg: Optional[ModelConfig] = None):
     from .chat_template import family_for
     mcfg = mcfg or get_config(cfg.model_path or cfg.model)
     return get_tokenizer(cfg.tokenizer, mcfg.vocab_size, mcfg.bos_token_id, mcfg.eos_token_id,
-                         family_for(mcfg.name, mcfg.is_moe))
+                         family_for(mcfg.name, mcfg.is_moe, mcfg.qk_norm))
 
 
 class LLMEngine:

@@ -177,6 +177,34 @@ class LlamaAttention(nn.Module):
         # FP8 KV cache: attention reads scale * byte (checkpoint k_scale / v_scale, replicated under TP)
         self.k_scale = 1.0
         self.v_scale = 1.0
+        # QK-norm (cfg.qk_norm, Qwen3): [head_dim] RMSNorm weights applied per head to q and k before
+        # RoPE, replicated under TP; None: a model without it, for which no QK-norm code runs
+        self.q_norm = None
+        self.k_norm = None
+        self.qk_eps = cfg.rms_eps
+
+    def slabs_ok(self, md: attn_ops.AttnMetadata, k_cache: torch.Tensor) -> bool:
+        """Whether this step's QKV may stay split-K slabs (:meth:`attend_slabs`): pure decode hands
+        them to the attention kernel (any cache), steps with prefill need the slab writer (bf16
+        cache).  A QK-norm model has only the slab writer."""
+        if self.q_norm is not None:
+            return attn_ops.slab_writers_ok(k_cache)
+        return md.num_prefill == 0 or attn_ops.slab_writers_ok(k_cache)
+
+    def attend_slabs(self, p: gemm.Partial, positions: torch.Tensor, md: attn_ops.AttnMetadata,
+                     cos_sin: torch.Tensor, kv: Tuple[torch.Tensor, torch.Tensor]) -> torch.Tensor:
+        """RoPE + KV-cache write + paged attention from the QKV projection's split-K slabs (after any
+        LoRA delta) -> [T, nq * hd].  Pure decode: the attention kernel does all of it in one launch.
+        Steps with prefill, and every step of a QK-norm model (whose norm only the slab writer
+        applies): the slab writer, then q-only paged attention."""
+        k_cache, v_cache = kv
+        if self.q_norm is None and md.num_prefill == 0:
+            return attn_ops.paged_decode_from_qkv(p, positions, cos_sin, k_cache, v_cache, md, self.scale,
+                                                  self.nq, self.nkv, k_scale=self.k_scale, v_scale=self.v_scale)
+        q = gemm.qkv_reduce_rope_cache(p, positions, cos_sin, k_cache, v_cache, md.slot_mapping, self.nq, self.nkv,
+                                       q_norm=self.q_norm, k_norm=self.k_norm, eps=self.qk_eps)
+        return attn_ops.paged_attention(q, k_cache, v_cache, md, self.scale, k_scale=self.k_scale,
+                                        v_scale=self.v_scale)
 
     def drop(self, a: torch.Tensor) -> torch.Tensor:
         return a.zero_() if self.fault_drop else a
@@ -192,22 +220,13 @@ class LlamaAttention(nn.Module):
         S = gemm.choose_split(self.qkv.shape[0], x.shape[1], T)
         # (a cache without the split-K epilogue writer: its steps with prefill take linear -> rope_and_cache)
         if (ws is not None and gemm.skinny_ok(x, self.qkv) and S > 1 and ws.numel() >= S * T * self.qkv.shape[0]
-                and (md.num_prefill == 0 or attn_ops.slab_writers_ok(k_cache))):
-            p = gemm.linear_partial(x, self.qkv, ws, S, packed=self.qkv_p)
-            if md.num_prefill == 0:
-                # pure decode: the attention kernel itself reduces the QKV slabs, applies RoPE
-                # and writes the new k / v into the paged cache
-                a = attn_ops.paged_decode_from_qkv(p, positions, cos_sin, k_cache, v_cache, md, self.scale,
-                                                   self.nq, self.nkv, k_scale=self.k_scale, v_scale=self.v_scale)
-                return _proj_out(self.drop(a), self.o, ws, self.o_p, half=True)
-            # split-K QKV whose epilogue kernel also applies RoPE and writes the KV cache
-            q = gemm.qkv_reduce_rope_cache(p, positions, cos_sin, k_cache, v_cache, md.slot_mapping, self.nq,
-                                           self.nkv)
-        else:
-            return _proj_out(self.drop(self.attend(gemm.linear(x, self.qkv, packed=self.qkv_p), positions, md,
-                                                   cos_sin, kv)), self.o, ws, self.o_p)
-        a = attn_ops.paged_attention(q, k_cache, v_cache, md, self.scale, k_scale=self.k_scale, v_scale=self.v_scale)
-        return _proj_out(self.drop(a), self.o, ws, self.o_p, half=True)
+                and self.slabs_ok(md, k_cache)):
+            # pure decode: the attention kernel itself reduces the QKV slabs, applies RoPE and writes
+            # the new k / v into the paged cache; else the split-K epilogue kernel does (attend_slabs)
+            a = self.attend_slabs(gemm.linear_partial(x, self.qkv, ws, S, packed=self.qkv_p), positions, md, cos_sin, kv)
+            return _proj_out(self.drop(a), self.o, ws, self.o_p, half=True)
+        return _proj_out(self.drop(self.attend(gemm.linear(x, self.qkv, packed=self.qkv_p), positions, md,
+                                               cos_sin, kv)), self.o, ws, self.o_p)
 
     def _forward_w8(self, x: torch.Tensor, positions: torch.Tensor, md: attn_ops.AttnMetadata, cos_sin: torch.Tensor,
                     kv: Tuple[torch.Tensor, torch.Tensor], ws: Optional[torch.Tensor]):
@@ -218,26 +237,19 @@ class LlamaAttention(nn.Module):
         N = self.qkv_p.shape[0]
         S = gemm.choose_split(N, x.shape[1], T)
         if (ws is not None and gemm_w8.kernel_ok(x, gemm.SKINNY_MAX_M) and S > 1 and ws.numel() >= S * T * N
-                and (md.num_prefill == 0 or attn_ops.slab_writers_ok(k_cache))):
-            p = gemm_w8.linear_partial(x, self.qkv_p, ws, S)
-            if md.num_prefill == 0:
-                a = attn_ops.paged_decode_from_qkv(p, positions, cos_sin, k_cache, v_cache, md, self.scale,
-                                                   self.nq, self.nkv, k_scale=self.k_scale, v_scale=self.v_scale)
-            else:
-                q = gemm.qkv_reduce_rope_cache(p, positions, cos_sin, k_cache, v_cache, md.slot_mapping, self.nq,
-                                               self.nkv)
-                a = attn_ops.paged_attention(q, k_cache, v_cache, md, self.scale, k_scale=self.k_scale,
-                                             v_scale=self.v_scale)
+                and self.slabs_ok(md, k_cache)):
+            a = self.attend_slabs(gemm_w8.linear_partial(x, self.qkv_p, ws, S), positions, md, cos_sin, kv)
             return _proj_out_w8(self.drop(a), self.o_p, ws, half=True)
         a = self.attend(gemm_w8.linear(x, self.qkv_p), positions, md, cos_sin, kv)
         return _proj_out_w8(self.drop(a), self.o_p, ws)
 
     def attend(self, qkv: torch.Tensor, positions: torch.Tensor, md: attn_ops.AttnMetadata, cos_sin: torch.Tensor,
                kv: Tuple[torch.Tensor, torch.Tensor]) -> torch.Tensor:
-        """RoPE + KV-cache write + paged attention from a projected [T, (nq + 2 nkv) hd] qkv."""
+        """(QK-norm +) RoPE + KV-cache write + paged attention from a projected [T, (nq + 2 nkv) hd] qkv."""
         k_cache, v_cache = kv
         attn_ops.rope_and_cache(qkv, positions, cos_sin, k_cache, v_cache, md.slot_mapping, self.nq, self.nkv,
-                                self.hd, k_scale=self.k_scale, v_scale=self.v_scale)
+                                self.hd, k_scale=self.k_scale, v_scale=self.v_scale, q_norm=self.q_norm,
+                                k_norm=self.k_norm, eps=self.qk_eps)
         q = qkv.view(qkv.shape[0], self.nq + 2 * self.nkv, self.hd)[:, :self.nq]
         return attn_ops.paged_attention(q, k_cache, v_cache, md, self.scale, k_scale=self.k_scale,
                                         v_scale=self.v_scale)
@@ -343,6 +355,10 @@ class LlamaForCausalLM(nn.Module):
             layer.attn.o = _p(cols(f"l{i}.o", (H, cfg.num_heads * hd)).contiguous())
             layer.ln1 = _p(torch.ones(H, dtype=dt, device=dev))
             layer.ln2 = _p(torch.ones(H, dtype=dt, device=dev))
+            if cfg.qk_norm:
+                # not ones: a model whose norm weights are ones cannot tell "ignored" from "applied"
+                layer.attn.q_norm = _p(weights.random_uniform(f"l{i}.q_norm", (hd,), 0.5, 1.5, seed, dev, dt))
+                layer.attn.k_norm = _p(weights.random_uniform(f"l{i}.k_norm", (hd,), 0.5, 1.5, seed, dev, dt))
             self._init_mlp_random(i, layer.mlp, rows, cols)
         return self
 
@@ -374,6 +390,15 @@ class LlamaForCausalLM(nn.Module):
             layer.ln1 = _p(get(p + "input_layernorm.weight"))
             layer.ln2 = _p(get(p + "post_attention_layernorm.weight"))
             layer.attn.k_scale, layer.attn.v_scale = weights.kv_scales(idx, p + "self_attn.")
+            if cfg.qk_norm:  # replicated under TP; a checkpoint without them is not this model
+                for n in ("q_norm", "k_norm"):
+                    if not idx.has(p + f"self_attn.{n}.weight"):
+                        raise KeyError(f"{path}: {p}self_attn.{n}.weight is missing from a qk_norm model")
+                layer.attn.q_norm = _p(get(p + "self_attn.q_norm.weight").contiguous())
+                layer.attn.k_norm = _p(get(p + "self_attn.k_norm.weight").contiguous())
+                for w in (layer.attn.q_norm, layer.attn.k_norm):
+                    if tuple(w.shape) != (cfg.head_dim,):
+                        raise ValueError(f"{p}self_attn q_norm / k_norm: expected [{cfg.head_dim}], got {tuple(w.shape)}")
             self._load_mlp_hf(i, layer.mlp, get, p)
         return self
 
@@ -398,6 +423,9 @@ class LlamaForCausalLM(nn.Module):
             out.update({p + "self_attn.q_proj.weight": q, p + "self_attn.k_proj.weight": k,
                         p + "self_attn.v_proj.weight": v, p + "self_attn.o_proj.weight": layer.attn.o,
                         p + "input_layernorm.weight": layer.ln1, p + "post_attention_layernorm.weight": layer.ln2})
+            if cfg.qk_norm:
+                out.update({p + "self_attn.q_norm.weight": layer.attn.q_norm,
+                            p + "self_attn.k_norm.weight": layer.attn.k_norm})
             for n in ("k_scale", "v_scale"):  # FP8 KV-cache scales: scalar fp32, written when not 1
                 if getattr(layer.attn, n) != 1.0:
                     out[p + "self_attn." + n] = torch.tensor(getattr(layer.attn, n), dtype=torch.float32)
@@ -416,7 +444,8 @@ class LlamaForCausalLM(nn.Module):
         from safetensors.torch import save_file
         os.makedirs(path, exist_ok=True)
         cfg = self.cfg
-        hf = {"architectures": ["MixtralForCausalLM" if cfg.is_moe else "LlamaForCausalLM"],
+        arch = "MixtralForCausalLM" if cfg.is_moe else ("Qwen3ForCausalLM" if cfg.qk_norm else "LlamaForCausalLM")
+        hf = {"architectures": [arch],
               "vocab_size": cfg.vocab_size, "hidden_size": cfg.hidden_size,
               "intermediate_size": cfg.intermediate_size, "num_hidden_layers": cfg.num_layers,
               "num_attention_heads": cfg.num_heads, "num_key_value_heads": cfg.num_kv_heads,
@@ -425,6 +454,8 @@ class LlamaForCausalLM(nn.Module):
               "bos_token_id": cfg.bos_token_id, "eos_token_id": cfg.eos_token_id, "_name_or_path": cfg.name}
         if cfg.is_moe:
             hf.update(num_local_experts=cfg.num_experts, num_experts_per_tok=cfg.experts_per_token)
+        if cfg.qk_norm:
+            hf.update(model_type="qwen3", attention_bias=False)
         if cfg.rope_scaling:
             hf["rope_scaling"] = cfg.rope_scaling
         with open(os.path.join(path, "config.json"), "w") as f:
@@ -451,8 +482,7 @@ class LlamaForCausalLM(nn.Module):
         # the folded chain serves decode batches up to DECODE_MAX_M rows; steps carrying prefill
         # chunks above 64 rows keep the library GEMMs (hipBLASLt) of the general path
         writers = not kv_caches or attn_ops.slab_writers_ok(kv_caches[0][0])
-        if (ws is not None and (md.num_prefill == 0 or (x.shape[0] <= gemm.SKINNY_MAX_M and writers))
-                and self._rowscale_ok(x)):
+        if ws is not None and self._chain_step_ok(md, x.shape[0], writers) and self._rowscale_ok(x):
             return self._forward_rowscale(x, positions, md, kv_caches, ws)
         residual = None
         for i, layer in enumerate(self.layers):
@@ -515,7 +545,7 @@ class LlamaForCausalLM(nn.Module):
         ws = self.workspace(T)
         writers = not kv_caches or attn_ops.slab_writers_ok(kv_caches[0][0])
         if (ws is not None and lora.ws_gu is not None and self._rowscale_ok(x)
-                and (md.num_prefill == 0 or (T <= gemm.SKINNY_MAX_M and writers))):
+                and self._chain_step_ok(md, T, writers)):
             return self._forward_rowscale_lora(x, positions, md, kv_caches, ws)
         # general path: bf16 projections, the delta added in the bf16 form; gate_up un-fused
         residual = None
@@ -559,13 +589,7 @@ class LlamaForCausalLM(nn.Module):
             p = gemm.linear_partial_rowscale(residual, at.qkv, ws, gemm.RowScale(parts, layer.eps),
                                              packed=at.qkv_pf, half=half)
             lora.add_slab(xn, p, i, "qkv")  # before RoPE, as it must
-            if md.num_prefill == 0:
-                a = attn_ops.paged_decode_from_qkv(p, positions, self.cos_sin, kc, vc, md, at.scale, at.nq, at.nkv,
-                                                   k_scale=at.k_scale, v_scale=at.v_scale)
-            else:
-                q = gemm.qkv_reduce_rope_cache(p, positions, self.cos_sin, kc, vc, md.slot_mapping, at.nq, at.nkv)
-                a = attn_ops.paged_attention(q, kc, vc, md, at.scale)
-            a = at.drop(a)
+            a = at.drop(at.attend_slabs(p, positions, md, self.cos_sin, kv_caches[i]))
             o = lora.add_slab(a, gemm.linear_partial(a, at.o, ws, packed=at.o_p, half=True), i, "o")
             parts = gemm.residual_parts(o, residual, buf2)
             xn = gemm.norm_apply(residual, parts, getattr(layer, "ln2_folded", layer.ln2), layer.eps)
@@ -625,6 +649,16 @@ class LlamaForCausalLM(nn.Module):
             lambda r, o, w=mlp.down, wp=mlp.down_p: gemm.linear(r, w, out=o, packed=wp), mlp.down.shape[0]))
 
     # ------------------------------------------------------------------ folded-norm decode chain
+    def _chain_step_ok(self, md: attn_ops.AttnMetadata, T: int, writers: bool) -> bool:
+        """Whether the folded chain may take this step: pure decode (the attention kernel reads the
+        QKV slabs, whatever the cache), or prefill rows within one 64-row tile when the cache has the
+        slab writer (``writers``, ops/attention.py slab_writers_ok).  A QK-norm model's slabs go
+        through the slab writer on every step, so its pure decode needs it too: with an FP8 cache
+        the general path serves it."""
+        if md.num_prefill == 0:
+            return writers or self.layers[0].attn.q_norm is None
+        return T <= gemm.SKINNY_MAX_M and writers
+
     def _rowscale_ok(self, x: torch.Tensor) -> bool:
         l0 = self.layers[0]
         if self.st.tp_size > 1:
@@ -683,6 +717,8 @@ class LlamaForCausalLM(nn.Module):
             return False
         if self.w8:  # FP8 weights: the two-launch forms only (the fused launches are bf16-only)
             return False
+        if at.q_norm is not None:  # QK-norm: the fused launch has no norm between the slab sum and RoPE
+            return False
         return (md.num_prefill == 0 and gemm.QKV_ATTN_FUSED and at.nkv >= gemm.QKV_ATTN_MIN_KV
                 and gemm.fused_rows_ok(T, nparts) and md.num_decode == T
                 and not (self.st.shared_device and self.st.tp_size > 1))
@@ -707,12 +743,9 @@ class LlamaForCausalLM(nn.Module):
             p = gemm_w8.linear_partial_rowscale(residual, at.qkv_pf, ws, rs, half=half)
         else:
             p = gemm.linear_partial_rowscale(residual, at.qkv, ws, rs, packed=at.qkv_pf, half=half)
-        if md.num_prefill == 0:
-            return attn_ops.paged_decode_from_qkv(p, positions, self.cos_sin, kc, vc, md, at.scale, at.nq, at.nkv,
-                                                  k_scale=at.k_scale, v_scale=at.v_scale)
-        # (asserts slab_writers_ok: an FP8 cache's steps with prefill take the general path, forward)
-        q = gemm.qkv_reduce_rope_cache(p, positions, self.cos_sin, kc, vc, md.slot_mapping, at.nq, at.nkv)
-        return attn_ops.paged_attention(q, kc, vc, md, at.scale)
+        # (steps with prefill and QK-norm models need slab_writers_ok: an FP8 cache sends them down the
+        # general path, forward)
+        return at.attend_slabs(p, positions, md, self.cos_sin, kv)
 
     def _decode_mlp(self, layer, residual: torch.Tensor, parts: torch.Tensor, ws: torch.Tensor) -> gemm.Partial:
         """Folded-norm gate_up + SiLU and the down projection of one layer -> down's split-K slabs."""
@@ -797,6 +830,8 @@ class LlamaForCausalLM(nn.Module):
         MLP launch) and whose QKV is not fused with the attention (70B TP=8: one kv head per rank).
         Ranks sharing a GPU keep the plain chain: a rank's consumer tiles wait inside a launch for
         its collective, whose peers' workgroups need slots on the same device."""
+        if self.layers[0].attn.q_norm is not None:  # the carried QKV feeds paged_decode_from_qkv: no QK-norm
+            return False
         on = self.carry_collectives
         if on is None:
             on = os.environ.get("POLYKEY_TP_CARRY", "0") in ("1", "gate_up") and not self.st.shared_device

@@ -34,6 +34,15 @@ def random_full(name: str, shape: Sequence[int], std: float, seed: int, device, 
     return t.to(dtype)
 
 
+def random_uniform(name: str, shape: Sequence[int], lo: float, hi: float, seed: int, device, dtype) -> torch.Tensor:
+    """A small replicated parameter uniform in [lo, hi] (the QK-norm weights), drawn on the CPU so
+    that every device and every TP rank holds the same values."""
+    g = torch.Generator(device="cpu")
+    g.manual_seed(_seed_for(seed, name))
+    t = torch.empty(tuple(shape), dtype=torch.float32).uniform_(lo, hi, generator=g)
+    return t.to(device=device, dtype=dtype)
+
+
 RANDOM_BLOCK = 128
 
 

@@ -111,18 +111,41 @@ def slab_writers_ok(k_cache: torch.Tensor) -> bool:
     return k_cache.dtype == torch.bfloat16
 
 
+def check_qk_norm(q_norm: torch.Tensor, k_norm: torch.Tensor, hd: int = 128) -> None:
+    """What the QK-norm entry points read: two contiguous [128] bf16 weights on the GPU, 16-byte
+    aligned (``rope_and_cache_kernel`` loads them as 16-byte vectors)."""
+    for w in (q_norm, k_norm):
+        if w.dtype != torch.bfloat16 or tuple(w.shape) != (hd,) or hd != 128 or not w.is_contiguous() or not w.is_cuda:
+            raise ValueError(f"QK-norm weights are contiguous [128] bfloat16 GPU tensors, got {tuple(w.shape)} "
+                             f"{w.dtype} on {w.device}")
+        if w.data_ptr() % 16:
+            raise ValueError("QK-norm weights must be 16-byte aligned (a view at an odd storage offset is not)")
+
+
 def rope_and_cache(qkv: torch.Tensor, positions: torch.Tensor, cos_sin: torch.Tensor, k_cache: torch.Tensor,
                    v_cache: torch.Tensor, slot_mapping: torch.Tensor, nq: int, nkv: int, hd: int = 128, *,
-                   k_scale: float = 1.0, v_scale: float = 1.0) -> None:
+                   k_scale: float = 1.0, v_scale: float = 1.0, q_norm: Optional[torch.Tensor] = None,
+                   k_norm: Optional[torch.Tensor] = None, eps: float = 1e-6) -> None:
     """In place on ``qkv`` [T, (nq+2nkv)*hd]; writes K/V of every token with slot >= 0.  An FP8
-    cache stores ``e4m3(clamp(x / scale, -448, 448))`` (the scales are ignored for bf16)."""
+    cache stores ``e4m3(clamp(x / scale, -448, 448))`` (the scales are ignored for bf16).
+    ``q_norm`` / ``k_norm`` ([128] bf16, both or neither) select the QK-norm entry point: every q and
+    k head is RMS-normalised with ``eps`` and weighted before the rotation (Qwen3)."""
+    if (q_norm is None) != (k_norm is None):
+        raise ValueError("q_norm and k_norm come together")
     if not qkv.is_cuda:
         reference.rope_and_cache(qkv, positions, cos_sin, k_cache, v_cache, slot_mapping, nq, nkv, hd,
-                                 k_scale=k_scale, v_scale=v_scale)
+                                 k_scale=k_scale, v_scale=v_scale, q_norm=q_norm, k_norm=k_norm, eps=eps)
         return
     T = qkv.shape[0]
     assert qkv.stride(-1) == 1 and positions.dtype == torch.int32 and slot_mapping.dtype == torch.int32
     assert cos_sin.dtype == torch.float32
+    if q_norm is not None:
+        check_qk_norm(q_norm, k_norm, hd)
+        native.call("pk_rope_and_cache_qknorm", qkv.data_ptr(), positions.data_ptr(), cos_sin.data_ptr(),
+                    k_cache.data_ptr(), v_cache.data_ptr(), slot_mapping.data_ptr(), q_norm.data_ptr(),
+                    k_norm.data_ptr(), float(eps), T, nq, nkv, hd, k_cache.shape[2], qkv.stride(0),
+                    *_kv_args(k_cache, v_cache, k_scale, v_scale), native.stream_ptr())
+        return
     native.call("pk_rope_and_cache", qkv.data_ptr(), positions.data_ptr(), cos_sin.data_ptr(), k_cache.data_ptr(),
                 v_cache.data_ptr(), slot_mapping.data_ptr(), T, nq, nkv, hd, k_cache.shape[2], qkv.stride(0),
                 *_kv_args(k_cache, v_cache, k_scale, v_scale), native.stream_ptr())

@@ -17,7 +17,7 @@ import torch
 import torch.nn.functional as F
 
 from . import native, reference
-from .attention import slab_writers_ok
+from .attention import check_qk_norm, slab_writers_ok
 
 import os
 
@@ -754,10 +754,22 @@ def silu_and_mul_interleaved(x: torch.Tensor, out: Optional[torch.Tensor] = None
 
 
 def qkv_reduce_rope_cache(p: Partial, positions: torch.Tensor, cos_sin: torch.Tensor, k_cache: torch.Tensor,
-                          v_cache: torch.Tensor, slots: torch.Tensor, nq: int, nkv: int) -> torch.Tensor:
-    """Split-K QKV epilogue: sum slabs, RoPE q/k, write k/v to the paged cache → q [M, nq, 128]."""
+                          v_cache: torch.Tensor, slots: torch.Tensor, nq: int, nkv: int, *,
+                          q_norm: Optional[torch.Tensor] = None, k_norm: Optional[torch.Tensor] = None,
+                          eps: float = 1e-6) -> torch.Tensor:
+    """Split-K QKV epilogue: sum slabs, RoPE q/k, write k/v to the paged cache → q [M, nq, 128].
+    ``q_norm`` / ``k_norm`` ([128] bf16, both or neither) select the QK-norm entry point: q and k
+    heads are RMS-normalised with ``eps`` and weighted between the slab sum and the rotation."""
     assert slab_writers_ok(k_cache) and slab_writers_ok(v_cache), "bf16 caches only (2-byte rows)"
+    if (q_norm is None) != (k_norm is None):
+        raise ValueError("q_norm and k_norm come together")
     q = torch.empty((p.M, nq, 128), dtype=torch.bfloat16, device=p.buf.device)
+    if q_norm is not None:
+        check_qk_norm(q_norm, k_norm)
+        native.call("pk_qkv_reduce_rope_cache_qknorm", q.data_ptr(), p.buf.data_ptr(), p.S, p.M, nq, nkv,
+                    positions.data_ptr(), cos_sin.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), slots.data_ptr(),
+                    k_cache.shape[2], q_norm.data_ptr(), k_norm.data_ptr(), float(eps), native.stream_ptr())
+        return q
     native.call("pk_qkv_reduce_rope_cache", q.data_ptr(), p.buf.data_ptr(), p.S, p.M, nq, nkv, positions.data_ptr(),
                 cos_sin.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), slots.data_ptr(), k_cache.shape[2],
                 native.stream_ptr())

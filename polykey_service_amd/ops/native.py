@@ -38,6 +38,8 @@ SIGNATURES = {
     "pk_silu_and_mul": [P, P, I32, I32, P],
     # the four attention launches end in kv_dtype (0: bf16, 1: e4m3 byte caches), k_scale, v_scale, stream
     "pk_rope_and_cache": [P, P, P, P, P, P, I32, I32, I32, I32, I32, I32, *KV, P],
+    # QK-norm (Qwen3): q_norm_w, k_norm_w, eps after the slot mapping
+    "pk_rope_and_cache_qknorm": [P, P, P, P, P, P, P, P, F32, I32, I32, I32, I32, I32, I32, *KV, P],
     "pk_paged_decode": [P, P, P, P, P, P, P, P, I32, I32, I32, I32, I32, I32, I32, F32, I32, *KV, P],
     "pk_set_decode_z": [I32],
     "pk_set_decode_fill": [I32],
@@ -67,6 +69,7 @@ SIGNATURES = {
     "pk_splitk_add_rmsnorm": [P, P, P, P, I32, I32, I32, F32, P],
     "pk_splitk_add_rmsnorm_route": [P, P, P, P, I32, I32, I32, F32, P, I32, I32, I32, P, P, P],
     "pk_qkv_reduce_rope_cache": [P, P, I32, I32, I32, I32, P, P, P, P, P, I32, P],
+    "pk_qkv_reduce_rope_cache_qknorm": [P, P, I32, I32, I32, I32, P, P, P, P, P, I32, P, P, F32, P],
     "pk_skinny_gemm_ex": [P, I32, P],
     "pk_mlp_fused": [P, P, P, P],
     "pk_qkv_attn_fused": [P, P, P, P, P, P, P, P, P, P, P, I32, I32, I32, I32, I32, F32, I32, P, P],

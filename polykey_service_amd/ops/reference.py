@@ -81,6 +81,19 @@ def apply_rope(x: torch.Tensor, positions: torch.Tensor, cos_sin: torch.Tensor) 
     return torch.cat([x1 * cos - x2 * sin, x2 * cos + x1 * sin], dim=-1).to(x.dtype)
 
 
+def qk_norm_rope(x: torch.Tensor, w: torch.Tensor, eps: float, positions: torch.Tensor, cos_sin: torch.Tensor,
+                 mutant: Optional[str] = None) -> torch.Tensor:
+    """QK-norm + RoPE of heads x [T, H, D] (the kernels' contract, csrc/kernels/rope_cache.hip):
+    y = x * rsqrt(mean(x^2) + eps) * w in fp32, rotated in fp32, rounded to x.dtype once.  (HF's
+    Qwen3 rounds y to the model dtype before rotating it; in fp32 the two agree.)"""
+    def norm(t):
+        return t * torch.rsqrt(t.pow(2).mean(-1, keepdim=True) + eps) * w.float()
+    xf = x.float()
+    if mutant == "after_rope":
+        return norm(apply_rope(xf, positions, cos_sin)).to(x.dtype)
+    return apply_rope(norm(xf), positions, cos_sin).to(x.dtype)
+
+
 _KIDX: dict = {}
 
 
@@ -186,14 +199,24 @@ def _store(cache_flat: torch.Tensor, index: tuple, rows: torch.Tensor, scale: fl
 def rope_and_cache(qkv: torch.Tensor, positions: torch.Tensor, cos_sin: torch.Tensor,
                    k_cache: Optional[torch.Tensor], v_cache: Optional[torch.Tensor],
                    slot_mapping: Optional[torch.Tensor], nq: int, nkv: int, hd: int,
-                   k_scale: float = 1.0, v_scale: float = 1.0) -> torch.Tensor:
+                   k_scale: float = 1.0, v_scale: float = 1.0, q_norm: Optional[torch.Tensor] = None,
+                   k_norm: Optional[torch.Tensor] = None, eps: float = 1e-6,
+                   mutant: Optional[str] = None) -> torch.Tensor:
     """Rotate q,k of the fused QKV output in place and scatter k,v into the paged cache (an FP8
-    cache gets the quantised values of the rotated, already rounded rows)."""
+    cache gets the quantised values of the rotated, already rounded rows).
+
+    ``q_norm`` / ``k_norm`` ([hd] weights, Qwen3 QK-norm): every q / k head is RMS-normalised and
+    weighted before the rotation, in fp32 with ONE rounding after norm + rotation
+    (:func:`qk_norm_rope`).  ``mutant`` (tests): ``"after_rope"`` normalises the rotated head."""
     T = qkv.shape[0]
     view = qkv.view(T, nq + 2 * nkv, hd)
     q, k, v = view[:, :nq], view[:, nq:nq + nkv], view[:, nq + nkv:]
-    q.copy_(apply_rope(q, positions, cos_sin))
-    k.copy_(apply_rope(k, positions, cos_sin))
+    if q_norm is not None:
+        q.copy_(qk_norm_rope(q, q_norm, eps, positions, cos_sin, mutant))
+        k.copy_(qk_norm_rope(k, k_norm, eps, positions, cos_sin, mutant))
+    else:
+        q.copy_(apply_rope(q, positions, cos_sin))
+        k.copy_(apply_rope(k, positions, cos_sin))
     if k_cache is not None and slot_mapping is not None:
         bs = k_cache.shape[2]
         sm = slot_mapping.long()

@@ -30,10 +30,10 @@ import os
 import uuid
 from typing import Any, Dict, List, Optional, Tuple
 
-from ..engine.chat_template import MISTRAL, ChatTemplate
+from ..engine.chat_template import CHATML, MISTRAL, ChatTemplate
 
 _DEC = json.JSONDecoder()
-_END_MARKERS = ("<|eom_id|>", "<|eot_id|>", "</s>", "<|end_of_text|>")
+_END_MARKERS = ("<|eom_id|>", "<|eot_id|>", "</s>", "<|end_of_text|>", "<|im_end|>", "<|endoftext|>")
 
 
 def _call(name: str, args: Any) -> Dict[str, Any]:
@@ -114,9 +114,12 @@ def forced_call(generated: str, name: Optional[str], allowed: List[str], family:
     """The call a forced prompt (``ChatTemplate.call_prefix``) produced: ``generated`` continues
     the opening, so for a named call it starts with the arguments."""
     g = _strip_end(generated)
+    if family == CHATML:  # the call's own closing tag
+        g = g.partition("</tool_call>")[0].rstrip()
     if name is None:  # the model wrote the name: re-assemble the whole call and parse it
         opening = '[{"name": "' if family == MISTRAL else '{"name": "'
-        _, calls = parse_tool_calls(("[TOOL_CALLS] " if family == MISTRAL else "") + opening + g, allowed)
+        lead = {MISTRAL: "[TOOL_CALLS] ", CHATML: "<tool_call>\n"}.get(family, "")
+        _, calls = parse_tool_calls(lead + opening + g, allowed)
         if calls:
             return calls[0]
         # no parseable call: the offered name the text starts with, else the first offered one
@@ -192,7 +195,7 @@ def strict_params(sp, tools, name: str, family: str):
     if not isinstance(schema, dict):
         schema = {"type": "object", "properties": {}}
     out = dataclasses.replace(sp, guided_regex=None, guided_choice=(), guided_json=json.dumps(schema, sort_keys=True),
-                              guided_suffix="}]" if family == MISTRAL else "}")
+                              guided_suffix={MISTRAL: "}]", CHATML: "}\n</tool_call>"}.get(family, "}"))
     out.validate(1 << 30)  # compiles the grammar: an unsupported schema fails the request here
     return out
 
