@@ -1,7 +1,7 @@
 // Weight-only FP8 (OCP e4m3, one fp32 scale per output channel) projections.
 //
 //   pk_w8_gemm     the decode GEMM on block-packed e4m3 weights: the W8 instantiations of the one
-//                  decode tile (skinny_tile.h skinny_tile, WFormat<true>) -- half the weight bytes
+//                  decode tile (skinny_tile.h skinny_tile, WFormat<kWFp8>) -- half the weight bytes
 //                  of the bf16 kernels, the same bf16 MFMA pipeline, the same three epilogues
 //   pk_w8_widen    packed bytes -> row-major bf16 [N, K] scratch (exact, no scale)   } the prefill
 //   pk_col_scale   out[m, n] = bf16(float(out[m, n]) * scale[n]), in place           } path
@@ -19,7 +19,7 @@ namespace {
 template <int MT, int MODE, bool NT, bool RS, int KR>
 __global__ void __launch_bounds__(256, 2) w8_gemm_kernel(const GemmW8Args args) {
   __shared__ SkinnyLds<MT> lds;
-  skinny_tile<MT, MODE, true, false, NT, RS, KR, 0, true>(args, blockIdx.x, 0, gridDim.x, lds, Flow{});
+  skinny_tile<MT, MODE, true, false, NT, RS, KR, 0, kWFp8>(args, blockIdx.x, 0, gridDim.x, lds, Flow{});
 }
 
 template <int MODE, bool NT, bool RS, int KR = 2>

@@ -1,6 +1,6 @@
 // The decode GEMM workgroup body (skinny_tile), its argument blocks and its tiling rules, shared by
-// the plain decode GEMM kernels (gemm_skinny.hip), the FP8-weight ones (gemm_w8.hip) and the fused
-// decode launches (decode_fused.hip, car_gemm.hip).
+// the plain decode GEMM kernels (gemm_skinny.hip), the FP8- and MXFP4-weight ones (gemm_w8.hip,
+// gemm_w4.hip) and the fused decode launches (decode_fused.hip, car_gemm.hip).
 #pragma once
 #include <type_traits>
 
@@ -54,6 +54,14 @@ struct GemmW8Args : GemmArgs {
   const float* w_scale;  // [N]
 };
 
+// MXFP4 weights (OCP Microscaling: e2m1 elements, one e8m0 scale byte per 32 elements along K; W4,
+// gemm_w4.hip):
+//   y[m, n] = sum_k x[m, k] * E2M1[nib[n, k]] * 2^(X[n, k / 32] - 127)      (fp32 products and sums)
+// W holds the block-packed nibbles, w_xscale the block-packed scale bytes (ops/gemm_w4.py pack_w4).
+struct GemmW4Args : GemmArgs {
+  const uint32_t* w_xscale;  // [N / 128, K / 128, 8 tiles, 16 rows] words of 4 e8m0 bytes
+};
+
 namespace {
 
 
@@ -95,6 +103,15 @@ __device__ __forceinline__ u32x4 ldw8(const fp8_t* p) {
   return *reinterpret_cast<const u32x4*>(p);
 }
 
+// the weight formats of the decode tile
+enum WFmt { kWBf16 = 0, kWFp8 = 1, kWMxfp4 = 2 };
+
+// a lane's MXFP4 data of one 16-row tile and 128-deep k-step: 32 nibbles and their 4 scale bytes
+struct W4Raw {
+  u32x4 q;     // word s: k = 32 s + 8 g .. + 7, low nibble first
+  uint32_t x;  // byte s: the e8m0 scale of k-block s of this lane's row
+};
+
 // What the tile knows about a weight format: a lane's 16-byte loads of one 16-row tile and 128-deep
 // k-step (kLoads of them, kStride elements apart in the packed layout, a lane's own at kLane * lane)
 // and the MFMA A fragment of k-block s (of 4) of that step.
@@ -105,25 +122,55 @@ __device__ __forceinline__ u32x4 ldw8(const fp8_t* p) {
 //   8 g .. + 7: the fragments of k-blocks 2 jj and 2 jj + 1, raw e4m3.  Activations stay bf16 and
 //   the MFMA is the bf16 one: a half is widened e4m3 -> bf16 (exact, kv_fp8.h fp8_widen8) right
 //   before the MFMAs that consume it.
-template <bool W8>
+//   MXFP4 (ops/gemm_w4.py pack_w4): per (128-row n-block, 128-deep k-step) the 8 KiB a workgroup
+//   consumes are contiguous, as 8 row tiles x 1 load of 1 KiB in lane order; lane l = 16 g + r holds
+//   row r, word s = the eight nibbles k = 32 s + 8 g .. + 7 (byte b: k + 2 b low, k + 2 b + 1 high):
+//   the fragment of k-block s, which is one MX block of that row.  Its scale byte is byte s of the
+//   lane's scale word.  A fragment is widened by four v_cvt_scalef32_pk_bf16_fp4 (two nibbles times
+//   2^(X - 127) -> two bf16; exact for 2 <= X <= 252, which the handle guarantees).
+//   kPer: weight elements per `elem`.
+template <WFmt F>
 struct WFormat {
   using elem = bf16_t;
   using raw = bf16x8_t;
-  static constexpr int kLoads = 4, kStride = 512, kLane = 8;
+  static constexpr int kLoads = 4, kStride = 512, kLane = 8, kPer = 1;
   template <bool NT>
   static __device__ __forceinline__ raw load(const elem* p) { return ldw<NT>(p); }
   static __device__ __forceinline__ bf16x8_t frag(const raw (&f)[kLoads], int s) { return f[s]; }
 };
 template <>
-struct WFormat<true> {
+struct WFormat<kWFp8> {
   using elem = fp8_t;
   using raw = u32x4;
-  static constexpr int kLoads = 2, kStride = 1024, kLane = 16;
+  static constexpr int kLoads = 2, kStride = 1024, kLane = 16, kPer = 1;
   template <bool NT>
   static __device__ __forceinline__ raw load(const elem* p) { return ldw8<NT>(p); }
   static __device__ __forceinline__ bf16x8_t frag(const raw (&f)[kLoads], int s) {
     const u32x4 v = f[s >> 1];
     return __builtin_bit_cast(bf16x8_t, fp8_widen8((s & 1) ? uint2{v[2], v[3]} : uint2{v[0], v[1]}));
+  }
+};
+// eight e2m1 nibbles of `word` times 2^(X - 127) -> 8 bf16 (X = the e8m0 byte; the convert reads its
+// scale as fp32, so the byte goes into the exponent field)
+__device__ __forceinline__ bf16x8_t mxfp4_widen8(uint32_t word, uint32_t X) {
+  const float sc = __builtin_bit_cast(float, X << 23);
+  const bf16x2_t a = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(word, sc, 0);
+  const bf16x2_t b = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(word, sc, 1);
+  const bf16x2_t c = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(word, sc, 2);
+  const bf16x2_t d = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(word, sc, 3);
+  return bf16x8_t{a[0], a[1], b[0], b[1], c[0], c[1], d[0], d[1]};
+}
+template <>
+struct WFormat<kWMxfp4> {
+  using elem = uint8_t;  // two nibbles
+  using raw = W4Raw;
+  static constexpr int kLoads = 1, kStride = 1024, kLane = 16, kPer = 2;
+  template <bool NT>
+  static __device__ __forceinline__ raw load(const elem* p, const uint32_t* x) {
+    return raw{ldw8<NT>(p), *x};
+  }
+  static __device__ __forceinline__ bf16x8_t frag(const raw (&f)[kLoads], int s) {
+    return mxfp4_widen8(f[0].q[s], (f[0].x >> (8 * s)) & 0xffu);
   }
 };
 
@@ -352,15 +399,17 @@ struct SkinnyLds {
 //      waits for every group its K range overlaps after requesting its first weight k-steps, and
 //      for ALL groups (`fw`, one counter) before the row scale, whose norm parts the collective
 //      writes too -- A and the parts read with sc1 loads
-// W8: FP8 weights (Args = GemmW8Args, WFormat<true>).  The format branches below are marked "W8:";
-// everything else -- row tiles, row-scale parts, A staging, both schedules, the epilogues -- is
-// written once for both formats.
-template <int MT, int MODE, bool PK, bool NORM, bool NT, bool RS = false, int KR = 2, int FL = 0, bool W8 = false,
+// WF: the weight format.  kWFp8: FP8 weights (Args = GemmW8Args); kWMxfp4: MXFP4 weights (Args =
+// GemmW4Args).  The format branches below are marked "W8:" (FP8 only), "W4:" (MXFP4 only) or "WQ:"
+// (both quantised formats); everything else -- row tiles, row-scale parts, A staging, both schedules,
+// the epilogues -- is written once for all formats.
+template <int MT, int MODE, bool PK, bool NORM, bool NT, bool RS = false, int KR = 2, int FL = 0, WFmt WF_ = kWBf16,
           class Args = GemmArgs>
 __device__ __forceinline__ void skinny_tile(const Args& args, const int bx_in, const int by, const int gdx,
                                             SkinnyLds<MT>& L, const Flow& fl, const Flow& fw = Flow{}) {
-  static_assert(!W8 || (PK && !NORM), "W8: block-packed weights, no norm prologue");
-  using WF = WFormat<W8>;
+  constexpr bool W8 = WF_ == kWFp8, W4 = WF_ == kWMxfp4, WQ = W8 || W4;
+  static_assert(!WQ || (PK && !NORM), "quantised weights: block-packed, no norm prologue");
+  using WF = WFormat<WF_>;
   using wel_t = typename WF::elem;
   constexpr int kWTile = WF::kLoads * WF::kStride;  // packed elements of one 16-row tile's k-step
   constexpr bool kProd = (FL & 1) != 0;
@@ -373,9 +422,9 @@ __device__ __forceinline__ void skinny_tile(const Args& args, const int bx_in, c
   auto& rinv_s = L.rinv;
   int& last_s = L.last;
   const int N = args.N, K = args.K, S = args.S;
-  // rows of this workgroup's group: all rows, or (grouped; bf16 only: the W8 kernels do not test
+  // rows of this workgroup's group: all rows, or (grouped; bf16 only: the WQ kernels do not test
   // for it, a dependent kernarg load ahead of everything else) expert by's
-  constexpr bool kMayGroup = !W8;
+  constexpr bool kMayGroup = !WQ;
   int gbeg = 0, gend = args.M;
   const wel_t* Wg = reinterpret_cast<const wel_t*>(args.W);
   if (kMayGroup && args.row_offsets != nullptr) {
@@ -434,9 +483,9 @@ __device__ __forceinline__ void skinny_tile(const Args& args, const int bx_in, c
       const int rr = min(64 * h + (tid >> 2), M - 1);
 #pragma unroll
       for (int q = 0; q < kRsLoads; ++q) {
-        // W8: one 32-bit index (<= 64 parts x 1024 rows), as for the A staging below: the address
+        // WQ: one 32-bit index (<= 64 parts x 1024 rows), as for the A staging below: the address
         // code is what the W8 kernels were measured with, and it shifts their loop schedule
-        const float* p = W8 ? args.nrm_parts + (min(sub + 4 * q, np - 1) * args.M + row0 + rr)
+        const float* p = WQ ? args.nrm_parts + (min(sub + 4 * q, np - 1) * args.M + row0 + rr)
                             : args.nrm_parts + min(sub + 4 * q, np - 1) * args.M + row0 + rr;
         rs_p[h * kRsLoads + q] = kWaitCar ? ldf_sc1(args.nrm_parts, p) : *p;  // (parts written in-launch)
       }
@@ -463,23 +512,30 @@ __device__ __forceinline__ void skinny_tile(const Args& args, const int bx_in, c
   const wel_t* wp[kR];
 #pragma unroll
   for (int t = 0; t < kR; ++t)
-    wp[t] = PK ? Wg + static_cast<int64_t>(n0 >> 7) * 128 * K + (((n0 & 127) >> 4) + t) * kWTile + WF::kLane * lane  // block-packed
+    wp[t] = PK ? Wg + static_cast<int64_t>(n0 >> 7) * 128 * K / WF::kPer + (((n0 & 127) >> 4) + t) * kWTile + WF::kLane * lane  // block-packed
                : Wg + static_cast<int64_t>(n0 + 16 * t + r) * K + 8 * g;                     // row-major [N, K]
+  // W4: this lane's scale word of tile t in k-step 0 (128 words per n-block and k-step)
+  const uint32_t* xp[W4 ? kR : 1];
+  if constexpr (W4) {
+#pragma unroll
+    for (int t = 0; t < kR; ++t)
+      xp[t] = args.w_xscale + (static_cast<int64_t>(n0 >> 7) * (K >> 7) * 8 + ((n0 & 127) >> 4) + t) * 16 + r;
+  }
 
   // A staging: MT*16 rows x kKA cols of 16-byte pieces over 256 threads
   constexpr int kPieces = (16 * MT * kPPR + 255) / 256;
   u32x4 stage[kPieces];
   u32x4 stage_w[NORM ? kPieces : 1];
   // Source of each staged piece (fixed across k-chunks): its row's pointer.
-  // W8: a 32-bit element offset from A instead, holding row and column (rows <= 1024).  With row
+  // WQ: a 32-bit element offset from A instead, holding row and column (rows <= 1024).  With row
   // pointers every MT = 8 W8 kernel needs 8 to 12 more VGPRs, and the slabs / row-scale / 128-row
   // n-block one (folded QKV above 64 rows) reaches 256 and spills in the loop.  (The bf16 tile would
   // probably gain the same registers: not measured.)
-  std::conditional_t<W8, int, const bf16_t*> asrc[kPieces];
+  std::conditional_t<WQ, int, const bf16_t*> asrc[kPieces];
 #pragma unroll
   for (int p = 0; p < kPieces; ++p) {
     const int src_row = min((tid + 256 * p) / kPPR, M - 1);
-    if constexpr (W8) {  // (not grouped: no a_rows)
+    if constexpr (WQ) {  // (not grouped: no a_rows)
       asrc[p] = src_row * args.lda + ((tid + 256 * p) % kPPR) * 8;
     } else {
       const int r_a = args.a_rows != nullptr ? args.a_rows[row0 + src_row] / args.a_row_div : src_row;
@@ -487,7 +543,7 @@ __device__ __forceinline__ void skinny_tile(const Args& args, const int bx_in, c
     }
   }
   auto a_src = [&](int p, int kc, int col) -> const bf16_t* {
-    if constexpr (W8)
+    if constexpr (WQ)
       return A + kc + asrc[p];
     else
       return asrc[p] + kc + col;
@@ -530,16 +586,23 @@ __device__ __forceinline__ void skinny_tile(const Args& args, const int bx_in, c
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt) acc[t][mt] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-  // one 128-deep k-step of weights per buffer, as loaded (W8: raw e4m3, widened at use)
+  // one 128-deep k-step of weights per buffer, as loaded (W8: raw e4m3, W4: raw nibbles and their
+  // scale word; widened at use)
   using wraw_t = typename WF::raw;
   wraw_t wa[kR][WF::kLoads], wb[kR][WF::kLoads];
   auto load_w = [&](wraw_t (&dst)[kR][WF::kLoads], int k) {
+    if constexpr (W4) {
+#pragma unroll
+      for (int t = 0; t < kR; ++t)
+        dst[t][0] = WF::template load<NT>(wp[t] + static_cast<int64_t>(k >> 7) * (8 * kWTile), xp[t] + (k >> 7) * 128);
+    } else {
 #pragma unroll
     for (int t = 0; t < kR; ++t)
 #pragma unroll
       for (int s = 0; s < WF::kLoads; ++s)
         dst[t][s] = PK ? WF::template load<NT>(wp[t] + static_cast<int64_t>(k >> 7) * (8 * kWTile) + s * WF::kStride)
                        : WF::template load<NT>(wp[t] + k + 32 * s);
+    }
   };
   auto mma_step = [&](const wraw_t (&wf)[kR][WF::kLoads], int buf, int kk) {
 #pragma unroll
@@ -656,7 +719,7 @@ __device__ __forceinline__ void skinny_tile(const Args& args, const int bx_in, c
   for (int mt = 0; mt < MT; ++mt) {
     const int m = 16 * mt + r;
     if (m >= M) continue;
-    if constexpr (W8) {  // the channel scale, before the row scale
+    if constexpr (W8) {  // the channel scale, before the row scale (W4: the scales are inside acc)
 #pragma unroll
       for (int t = 0; t < kR; ++t) {
         acc[t][mt][0] *= sc_n[t].x;
@@ -746,8 +809,8 @@ __device__ __forceinline__ void skinny_tile(const Args& args, const int bx_in, c
   }
 }
 
-// The tiling rules of the plain decode GEMM launches, for both weight formats (dispatch in
-// gemm_skinny.hip, dispatch_w8 in gemm_w8.hip).  `rows` is the largest group's row count (dense:
+// The tiling rules of the plain decode GEMM launches, for every weight format (dispatch in
+// gemm_skinny.hip, dispatch_w8 in gemm_w8.hip, dispatch_w4 in gemm_w4.hip).  `rows` is the largest group's row count (dense:
 // M).  Sets a.tile_rows / a.row_tiles and decodes the tiling bits of `mode`; false: a shape that is
 // not tiled.
 struct SkinnyTiling {

@@ -42,7 +42,7 @@ class ServerConfig:
     gpu_mem_fraction: float = 0.90
     num_kv_blocks: int = 0         # 0 → size from free HBM
     kv_cache_dtype: str = "auto"   # auto | bf16 | fp8 (alias fp8_e4m3): KV-cache element type
-    weight_dtype: str = "auto"     # auto | bf16 | fp8 (alias fp8_e4m3): projection weight element type
+    weight_dtype: str = "auto"     # auto | bf16 | fp8 (alias fp8_e4m3) | mxfp4: projection weight element type
     # LoRA adapters served next to the model: "name=path[,name=path...]" (PEFT directories), all
     # resident; OpenAI "model": "<name>" / "llm.chat:<name>" / parameters.lora pick one
     lora_modules: str = ""
@@ -108,18 +108,21 @@ def normalize_kv_cache_dtype(value: str) -> str:
     raise ValueError(f"kv_cache_dtype must be one of {', '.join(KV_CACHE_DTYPES)} (got {value!r})")
 
 
-WEIGHT_DTYPES = ("auto", "bf16", "fp8")
+WEIGHT_DTYPES = ("auto", "bf16", "fp8", "mxfp4")
 
 
 def normalize_weight_dtype(value: str) -> str:
-    """``--weight-dtype`` / ``POLYKEY_WEIGHT_DTYPE`` -> "bf16" or "fp8".  "auto" means bf16 and
-    "fp8_e4m3" is an alias of "fp8" (weight-only OCP e4m3, one scale per output channel); anything
+    """``--weight-dtype`` / ``POLYKEY_WEIGHT_DTYPE`` -> "bf16", "fp8" or "mxfp4".  "auto" means bf16,
+    "fp8_e4m3" is an alias of "fp8" (weight-only OCP e4m3, one scale per output channel) and "mxfp4"
+    (weight-only OCP Microscaling FP4: e2m1 elements, one e8m0 scale per 32) has no alias; anything
     else is an error."""
     v = str(value).strip().lower()
     if v in ("auto", "bf16"):
         return "bf16"
     if v in ("fp8", "fp8_e4m3"):
         return "fp8"
+    if v == "mxfp4":
+        return "mxfp4"
     raise ValueError(f"weight_dtype must be one of {', '.join(WEIGHT_DTYPES)} (got {value!r})")
 
 

@@ -20,6 +20,7 @@ from ..config.server_config import (env_weight_dtype, normalize_kv_cache_dtype, 
                                     parse_lora_modules)
 from ..models import build_model
 from ..models.config import ModelConfig, get_config
+from ..models.llama import QUANT_FORMATS
 from ..ops.sampler import logprob_entry
 from ..parallel.state import ParallelState, get_state
 from . import grammar
@@ -47,7 +48,8 @@ class EngineConfig:
     # k_scale / v_scale, half the bytes per token (README "KV cache dtype")
     kv_cache_dtype: str = "auto"
     # projection weight element type: "auto" | "bf16" | "fp8" ("fp8_e4m3"): weight-only OCP e4m3 with
-    # one fp32 scale per output channel, quantised at set-up (README "Weight dtype").  Opt-in; a
+    # one fp32 scale per output channel | "mxfp4": weight-only OCP Microscaling FP4 (e2m1, one e8m0
+    # scale per 32 elements), quantised at set-up (README "Weight dtype").  Opt-in; a
     # config built without it takes POLYKEY_WEIGHT_DTYPE (config/server_config.py env_weight_dtype),
     # so with that variable set to fp8 every engine of the process asks for FP8 weights, and one
     # that cannot have them (MoE, TP, EP) raises instead of quietly serving bf16
@@ -100,15 +102,20 @@ class LLMEngine:
         self.cfg = cfg
         self.st = st or get_state()
         mcfg: ModelConfig = get_config(cfg.model_path or cfg.model)
-        if cfg.weight_dtype == "fp8":
-            # weight-only FP8 covers the dense Llama projections on one GPU; no silent fallback
+        wd = cfg.weight_dtype
+        quantised = wd in QUANT_FORMATS
+        if quantised:
+            # weight-only FP8 / MXFP4 cover the dense Llama projections on one GPU; no silent fallback
+            label = QUANT_FORMATS[wd].label
             if mcfg.is_moe:
-                raise ValueError(f"weight_dtype=fp8 does not support MoE models ({mcfg.name}): the grouped "
+                raise ValueError(f"weight_dtype={wd} does not support MoE models ({mcfg.name}): the grouped "
                                  "expert GEMMs are bf16-only")
             if self.st.tp_size > 1:
-                raise ValueError(f"weight_dtype=fp8 does not support tp={self.st.tp_size}: FP8 weights are not sharded")
+                raise ValueError(f"weight_dtype={wd} does not support tp={self.st.tp_size}: {label} weights are "
+                                 "not sharded")
             if self.st.ep_size > 1:
-                raise ValueError(f"weight_dtype=fp8 does not support ep={self.st.ep_size}: FP8 weights are not sharded")
+                raise ValueError(f"weight_dtype={wd} does not support ep={self.st.ep_size}: {label} weights are "
+                                 "not sharded")
         if cfg.lora_modules:
             # adapters cover the dense Llama projections in bf16 on one GPU; no silent fallback
             if mcfg.is_moe:
@@ -120,8 +127,9 @@ class LLMEngine:
             if self.st.ep_size > 1:
                 raise ValueError(f"LoRA adapters do not support ep={self.st.ep_size} yet: adapters are not "
                                  "sharded (a follow-up)")
-            if cfg.weight_dtype == "fp8":
-                raise ValueError("LoRA adapters do not support weight_dtype=fp8 yet: the W8 chain has no "
+            if quantised:
+                raise ValueError(f"LoRA adapters do not support weight_dtype={wd} yet: the "
+                                 f"{'W8' if wd == 'fp8' else 'W4'} chain has no "
                                  "adapter path (a follow-up; use weight_dtype=bf16)")
         if cfg.num_layers > 0 and cfg.num_layers != mcfg.num_layers:
             mcfg = dataclasses.replace(mcfg, num_layers=cfg.num_layers)
@@ -167,17 +175,18 @@ class LLMEngine:
             else:
                 model.init_random(cfg.seed)
         self.model = model
-        if cfg.weight_dtype == "fp8":
+        held = getattr(model, "quantised_dtype", None)  # the format a handed-over model already holds
+        if held is not None and held != wd:
+            raise ValueError(f"weight_dtype={wd} with a model whose projections are already "
+                             f"{QUANT_FORMATS[held].label}: pass weight_dtype={held}")
+        if quantised:
             if not hasattr(model, "weight_dtype"):
-                raise ValueError(f"weight_dtype=fp8 is not supported by {type(model).__name__}")
-            model.weight_dtype = "fp8"  # before pack_decode_weights, which quantises
-        elif getattr(model, "w8", False):
-            raise ValueError(f"weight_dtype={cfg.weight_dtype} with a model whose projections are already FP8: "
-                             "pass weight_dtype=fp8")
+                raise ValueError(f"weight_dtype={wd} is not supported by {type(model).__name__}")
+            model.weight_dtype = wd  # before pack_decode_weights, which quantises
         if hasattr(model, "pack_decode_weights"):
             model.pack_decode_weights()
         self.weight_bytes = model.projection_bytes() if hasattr(model, "projection_bytes") else 0
-        if cfg.weight_dtype != "fp8":
+        if not quantised:
             logging.getLogger(__name__).info("weights: dtype %s, %d projection bytes, 0 widen-scratch bytes",
                                              cfg.weight_dtype, self.weight_bytes)
         # LoRA adapters: loaded and made resident here, before the KV cache is sized

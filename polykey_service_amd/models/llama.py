@@ -27,6 +27,8 @@ QKV / gate_up weights and every projection is the hand-written weight-streaming 
 With ``weight_dtype = "fp8"`` (TP = 1) the four projections are weight-only FP8 handles
 (ops/gemm_w8.py): the same chain in its two-launch forms on the W8 decode GEMM (gemm_w8.hip), the
 general path on the same kernel up to 512 rows and on widen -> library GEMM -> column scale above.
+``weight_dtype = "mxfp4"`` is the same chain on MXFP4 handles (ops/gemm_w4.py, gemm_w4.hip; its wide
+path is widen -> library GEMM): both formats run one code path, dispatched on the handle's ops module.
 
 Vocab-parallel embedding and LM head for TP>1 (logits all-gathered for sampling).
 """
@@ -35,7 +37,7 @@ from __future__ import annotations
 import logging
 import math
 import os
-from typing import List, Optional, Tuple
+from typing import List, NamedTuple, Optional, Tuple
 
 import torch
 import torch.nn.functional as F
@@ -45,6 +47,7 @@ from .. import ops
 from ..ops import attention as attn_ops
 from ..ops import gemm
 from ..ops import gemm_prefill
+from ..ops import gemm_w4
 from ..ops import gemm_w8
 from ..ops import moe as moe_ops
 from ..ops import reference
@@ -136,17 +139,42 @@ def pack_folded(owner, name: str, norm_w: torch.Tensor, packed_only: bool) -> to
     return out
 
 
-def _proj_out_w8(x: torch.Tensor, w: gemm_w8.W8, ws: Optional[torch.Tensor], half: bool = False):
-    """:func:`_proj_out` on FP8 weights (TP = 1): decode-sized M returns the split-K slabs
-    unreduced, anything else bf16 (the W8 kernel, or its wide path above its row limit)."""
+class QuantFormat(NamedTuple):
+    ops: object      # the ops module of its handles (gemm_w8 / gemm_w4: the same functions on both)
+    handle: type     # the handle class
+    label: str       # how messages name the format
+    described: str   # how the start-up line names it
+
+
+# the weight dtypes whose projections are quantised at set-up: the one table of them (the engine's
+# checks and messages read it too)
+QUANT_FORMATS = {
+    "fp8": QuantFormat(gemm_w8, gemm_w8.W8, "FP8", "fp8 (e4m3, per-channel scales)"),
+    "mxfp4": QuantFormat(gemm_w4, gemm_w4.W4, "MXFP4", "mxfp4 (e2m1, one e8m0 scale per 32)"),
+}
+
+
+def quant_ops(w):
+    """The ops module of a quantised projection handle (gemm_w8 / gemm_w4: the same functions on
+    both formats); None for a tensor."""
+    for f in QUANT_FORMATS.values():
+        if isinstance(w, f.handle):
+            return f.ops
+    return None
+
+
+def _proj_out_q(x: torch.Tensor, w, ws: Optional[torch.Tensor], half: bool = False):
+    """:func:`_proj_out` on quantised weights (TP = 1): decode-sized M returns the split-K slabs
+    unreduced, anything else bf16 (the format's kernel, or its wide path above its row limit)."""
+    q = quant_ops(w)
     M, N = x.shape[0], w.shape[0]
-    if ws is not None and gemm_w8.kernel_ok(x, gemm.SKINNY_MAX_M) and gemm.norm_fusable(N):
+    if ws is not None and q.kernel_ok(x, gemm.SKINNY_MAX_M) and gemm.norm_fusable(N):
         S, _ = gemm.partial_tiling(N, x.shape[1], M, w.packed, half)
         if ws.numel() >= S * M * N:
-            return gemm_w8.linear_partial(x, w, ws, half=half)
+            return q.linear_partial(x, w, ws, half=half)
     # unsplit, o / down have too few n-blocks for the chip: above 64 rows the wide path is the
     # faster one (8B down at 256 rows: 84 vs 145 us, profiles/w8_gemm.md), as hipBLASLt is for bf16
-    return gemm_w8.linear(x, w, max_m=gemm.SKINNY_MAX_M)
+    return q.linear(x, w, max_m=gemm.SKINNY_MAX_M)
 
 
 def add_norm(pending, residual: torch.Tensor, w: torch.Tensor, eps: float):
@@ -215,8 +243,8 @@ class LlamaAttention(nn.Module):
         split-K :class:`~polykey_service_amd.ops.gemm.Partial` consumed by the next norm."""
         T = x.shape[0]
         k_cache, v_cache = kv
-        if isinstance(self.qkv_p, gemm_w8.W8):
-            return self._forward_w8(x, positions, md, cos_sin, kv, ws)
+        if quant_ops(self.qkv_p) is not None:
+            return self._forward_q(x, positions, md, cos_sin, kv, ws)
         S = gemm.choose_split(self.qkv.shape[0], x.shape[1], T)
         # (a cache without the split-K epilogue writer: its steps with prefill take linear -> rope_and_cache)
         if (ws is not None and gemm.skinny_ok(x, self.qkv) and S > 1 and ws.numel() >= S * T * self.qkv.shape[0]
@@ -228,20 +256,22 @@ class LlamaAttention(nn.Module):
         return _proj_out(self.drop(self.attend(gemm.linear(x, self.qkv, packed=self.qkv_p), positions, md,
                                                cos_sin, kv)), self.o, ws, self.o_p)
 
-    def _forward_w8(self, x: torch.Tensor, positions: torch.Tensor, md: attn_ops.AttnMetadata, cos_sin: torch.Tensor,
-                    kv: Tuple[torch.Tensor, torch.Tensor], ws: Optional[torch.Tensor]):
-        """:meth:`forward` on FP8 weights (``qkv_p`` / ``o_p`` are :class:`gemm_w8.W8` handles with
-        ln1 folded into QKV; ``x`` is normalised with unit weights): the same launches, W8 GEMMs."""
+    def _forward_q(self, x: torch.Tensor, positions: torch.Tensor, md: attn_ops.AttnMetadata, cos_sin: torch.Tensor,
+                   kv: Tuple[torch.Tensor, torch.Tensor], ws: Optional[torch.Tensor]):
+        """:meth:`forward` on quantised weights (``qkv_p`` / ``o_p`` are :class:`gemm_w8.W8` or
+        :class:`gemm_w4.W4` handles with ln1 folded into QKV; ``x`` is normalised with unit weights):
+        the same launches, the format's GEMMs."""
+        q = quant_ops(self.qkv_p)
         T = x.shape[0]
         k_cache, v_cache = kv
         N = self.qkv_p.shape[0]
         S = gemm.choose_split(N, x.shape[1], T)
-        if (ws is not None and gemm_w8.kernel_ok(x, gemm.SKINNY_MAX_M) and S > 1 and ws.numel() >= S * T * N
+        if (ws is not None and q.kernel_ok(x, gemm.SKINNY_MAX_M) and S > 1 and ws.numel() >= S * T * N
                 and self.slabs_ok(md, k_cache)):
-            a = self.attend_slabs(gemm_w8.linear_partial(x, self.qkv_p, ws, S), positions, md, cos_sin, kv)
-            return _proj_out_w8(self.drop(a), self.o_p, ws, half=True)
-        a = self.attend(gemm_w8.linear(x, self.qkv_p), positions, md, cos_sin, kv)
-        return _proj_out_w8(self.drop(a), self.o_p, ws)
+            a = self.attend_slabs(q.linear_partial(x, self.qkv_p, ws, S), positions, md, cos_sin, kv)
+            return _proj_out_q(self.drop(a), self.o_p, ws, half=True)
+        a = self.attend(q.linear(x, self.qkv_p), positions, md, cos_sin, kv)
+        return _proj_out_q(self.drop(a), self.o_p, ws)
 
     def attend(self, qkv: torch.Tensor, positions: torch.Tensor, md: attn_ops.AttnMetadata, cos_sin: torch.Tensor,
                kv: Tuple[torch.Tensor, torch.Tensor]) -> torch.Tensor:
@@ -265,8 +295,9 @@ class LlamaMLP(nn.Module):
         self.gate_up_pf = None  # block-packed with ln2 folded in (FOLD_NORM)
 
     def forward(self, x: torch.Tensor, ws: Optional[torch.Tensor] = None):
-        if isinstance(self.gate_up_p, gemm_w8.W8):  # FP8 weights (ln2 folded into gate_up)
-            return _proj_out_w8(gemm_w8.linear_silu(x, self.gate_up_p, ws), self.down_p, ws)
+        q = quant_ops(self.gate_up_p)
+        if q is not None:  # quantised weights (ln2 folded into gate_up)
+            return _proj_out_q(q.linear_silu(x, self.gate_up_p, ws), self.down_p, ws)
         h = gemm.linear_silu(x, self.gate_up, ws, packed=self.gate_up_p)  # gate/up rows interleaved by 16
         return _proj_out(h, self.down, ws, self.down_p)
 
@@ -313,10 +344,12 @@ class LlamaForCausalLM(nn.Module):
         self.norm = None
         self.lm_head = None
         self.lm_head_p = None  # block-packed decode copy (pack_decode_weights)
-        # projection weight element type: "bf16", or "fp8" (weight-only OCP e4m3, one scale per output
-        # channel: pack_decode_weights quantises; set before it runs -- README "Weight dtype")
+        # projection weight element type: "bf16", "fp8" (weight-only OCP e4m3, one scale per output
+        # channel) or "mxfp4" (weight-only OCP Microscaling FP4): pack_decode_weights quantises; set
+        # before it runs -- README "Weight dtype"
         self.weight_dtype = "bf16"
         self.w8 = False  # the projections are gemm_w8.W8 handles
+        self.quantised_dtype = None  # the weight_dtype whose handles the projections are ("fp8" / "mxfp4")
         # resident LoRA adapters (models/lora.py LoraState, enable_lora); None: no adapters configured
         self.lora = None
         self.register_buffer("cos_sin", reference.rope_cos_sin_cache(cfg.max_position, cfg.head_dim, cfg.rope_theta,
@@ -514,8 +547,9 @@ class LlamaForCausalLM(nn.Module):
         if self.st.tp_size > 1 or self.st.ep_size > 1:
             raise ValueError(f"LoRA adapters do not support tp={self.st.tp_size} / ep={self.st.ep_size} yet: "
                              "adapters are not sharded (a follow-up)")
-        if self.w8 or self.weight_dtype == "fp8":
-            raise ValueError("LoRA adapters do not support weight_dtype=fp8 yet (a follow-up; use weight_dtype=bf16)")
+        if self.wq is not None or self.weight_dtype in QUANT_FORMATS:
+            wd = self.quantised_dtype or self.weight_dtype
+            raise ValueError(f"LoRA adapters do not support weight_dtype={wd} yet (a follow-up; use weight_dtype=bf16)")
         if getattr(self, "packed_only", False):
             raise ValueError("LoRA adapters need the row-major projection weights next to the block-packed "
                              "ones (POLYKEY_PACKED_WEIGHTS=packed keeps only the packed copies)")
@@ -698,8 +732,8 @@ class LlamaForCausalLM(nn.Module):
             # profiles/r2_decode_ab.txt: fewer fp32 slab bytes written and re-read); the residual
             # update inside the O launch (1 % slower, profiles/r4_o_inlaunch_ab.jsonl) and as phase 0
             # of the fused launches (3 % slower, profiles/r5_phase_ab.jsonl) were removed in round 6
-            if self.w8:
-                o = gemm_w8.linear_partial(a, layer.attn.o_p, ws, half=True)
+            if self.wq is not None:
+                o = self.wq.linear_partial(a, layer.attn.o_p, ws, half=True)
             else:
                 o = gemm.linear_partial(a, layer.attn.o, ws, packed=layer.attn.o_p, half=True)
             parts = gemm.residual_parts(o, residual, buf2)
@@ -715,7 +749,7 @@ class LlamaForCausalLM(nn.Module):
         # kc: the K cache the step writes (ops/attention.py slab_writers_ok)
         if kc is not None and not attn_ops.slab_writers_ok(kc):
             return False
-        if self.w8:  # FP8 weights: the two-launch forms only (the fused launches are bf16-only)
+        if self.wq is not None:  # quantised weights: the two-launch forms only (the fused launches are bf16-only)
             return False
         if at.q_norm is not None:  # QK-norm: the fused launch has no norm between the slab sum and RoPE
             return False
@@ -739,8 +773,8 @@ class LlamaForCausalLM(nn.Module):
         # TP=8 shard's 10 n-blocks otherwise take split 16; one 64-row tile only: the row-tiled wide
         # batches keep 128-row n-blocks, 8B at 256 rows 34.5 vs 26 us, profiles/r5_wide_256_kgrid.md)
         half = gemm.QKV_HALF and T <= gemm.SKINNY_MAX_M
-        if self.w8:
-            p = gemm_w8.linear_partial_rowscale(residual, at.qkv_pf, ws, rs, half=half)
+        if self.wq is not None:
+            p = self.wq.linear_partial_rowscale(residual, at.qkv_pf, ws, rs, half=half)
         else:
             p = gemm.linear_partial_rowscale(residual, at.qkv, ws, rs, packed=at.qkv_pf, half=half)
         # (steps with prefill and QK-norm models need slab_writers_ok: an FP8 cache sends them down the
@@ -751,9 +785,9 @@ class LlamaForCausalLM(nn.Module):
         """Folded-norm gate_up + SiLU and the down projection of one layer -> down's split-K slabs."""
         mlp = layer.mlp
         rs = gemm.RowScale(parts, layer.eps)
-        if self.w8:  # FP8 weights: gate_up + SiLU, then down, as two W8 launches
-            h = gemm_w8.linear_silu(residual, mlp.gate_up_pf, ws=self._ws_gu, rowscale=rs)
-            return gemm_w8.linear_down(h, mlp.down_p, ws)
+        if self.wq is not None:  # quantised weights: gate_up + SiLU, then down, as two launches of the format's GEMM
+            h = self.wq.linear_silu(residual, mlp.gate_up_pf, ws=self._ws_gu, rowscale=rs)
+            return self.wq.linear_down(h, mlp.down_p, ws)
         if gemm.mlp_fused_ok(residual, mlp.gate_up_pf, mlp.down_p, parts.shape[0]) and not self.st.shared_device:
             # gate_up + SiLU and the down slabs in one launch (down's launch ramp hidden)
             return gemm.mlp_fused(residual, mlp.gate_up_pf, mlp.down_p, rs, ws, self._flow)
@@ -1017,12 +1051,13 @@ class LlamaForCausalLM(nn.Module):
         with unit weights (``ln1`` / ``ln2`` become ones; the originals stay as ``ln*_folded``).
         ``POLYKEY_PACKED_WEIGHTS`` = auto | 1 (both copies) | packed (packed only) | 0.
 
-        With ``weight_dtype == "fp8"`` the projections are quantised instead
+        With ``weight_dtype`` "fp8" or "mxfp4" the projections are quantised instead
         (:meth:`_quantise_projections`), on any device and whatever that variable says."""
-        if self.w8 and self.weight_dtype != "fp8":
-            raise ValueError("this model's projections are already FP8 (weight_dtype=fp8); it cannot serve "
-                             f"weight_dtype={self.weight_dtype}")
-        if self.weight_dtype == "fp8":
+        held = self.quantised_dtype
+        if held is not None and self.weight_dtype != held:
+            raise ValueError(f"this model's projections are already {QUANT_FORMATS[held].label} "
+                             f"(weight_dtype={held}); it cannot serve weight_dtype={self.weight_dtype}")
+        if self.weight_dtype in QUANT_FORMATS:
             return self._quantise_projections()
         mode = mode or os.environ.get("POLYKEY_PACKED_WEIGHTS", "auto")
         if mode == "0" or self.device.type != "cuda" or not gemm.SKINNY_ENABLED:
@@ -1069,8 +1104,9 @@ class LlamaForCausalLM(nn.Module):
         return True
 
     def _quantise_projections(self) -> bool:
-        """``weight_dtype="fp8"``: the four dense projections of every layer become weight-only
-        FP8 (:class:`gemm_w8.W8`: block-packed OCP e4m3 bytes, one fp32 scale per output channel),
+        """``weight_dtype="fp8"`` / ``"mxfp4"``: the four dense projections of every layer become
+        weight-only FP8 (:class:`gemm_w8.W8`: block-packed OCP e4m3 bytes, one fp32 scale per output
+        channel) or MXFP4 (:class:`gemm_w4.W4`: block-packed e2m1 nibbles, one e8m0 scale per 32),
         quantised once, after the RMSNorm fold: ``qkv_pf`` / ``gate_up_pf`` =
         quantise(fold_norm(w, ln)) -- one rounding -- and o / down unfolded.  As in the packed-only
         mode the row-major attributes become meta placeholders, freed projection by projection,
@@ -1078,23 +1114,25 @@ class LlamaForCausalLM(nn.Module):
         head and norm weights stay bf16.  On the GPU the widen scratch of the prefill path (the
         largest projection, bf16) is reserved here, before the KV cache is sized.  Works on any
         device: CPU tensors take the fp32 reference ops."""
-        if self.w8:  # already quantised (a model handed from one engine to the next)
+        if self.wq is not None:  # already quantised (a model handed from one engine to the next)
             return True
+        wd = self.weight_dtype
+        q, handle, name_, label = QUANT_FORMATS[wd]
         if self.st.tp_size > 1 or self.st.ep_size > 1:
-            raise ValueError(f"weight_dtype=fp8 does not support tp={self.st.tp_size} / ep={self.st.ep_size}: "
-                             "FP8 weights are not sharded (use weight_dtype=bf16)")
+            raise ValueError(f"weight_dtype={wd} does not support tp={self.st.tp_size} / ep={self.st.ep_size}: "
+                             f"{name_} weights are not sharded (use weight_dtype=bf16)")
         if not isinstance(self.layers[0].mlp, LlamaMLP):
-            raise ValueError("weight_dtype=fp8 does not support MoE models: the grouped expert GEMMs are "
+            raise ValueError(f"weight_dtype={wd} does not support MoE models: the grouped expert GEMMs are "
                              "bf16-only (use weight_dtype=bf16)")
         l0 = self.layers[0]
         for w in (l0.attn.qkv, l0.attn.o, l0.mlp.gate_up, l0.mlp.down):
             if w.shape[0] % 128 or w.shape[1] % 256:
-                raise ValueError(f"weight_dtype=fp8 needs projections of N % 128 == 0 and K % 256 == 0 "
+                raise ValueError(f"weight_dtype={wd} needs projections of N % 128 == 0 and K % 256 == 0 "
                                  f"(got {tuple(w.shape)})")
 
-        def quantise(owner, name: str, norm_w: Optional[torch.Tensor] = None) -> gemm_w8.W8:
+        def quantise(owner, name: str, norm_w: Optional[torch.Tensor] = None):
             src = getattr(owner, name)
-            out = gemm_w8.W8.from_weight(src if norm_w is None else gemm.fold_norm(src, norm_w))
+            out = handle.from_weight(src if norm_w is None else gemm.fold_norm(src, norm_w))
             setattr(owner, name, _p(torch.empty(src.shape, dtype=src.dtype, device="meta")))
             return out
 
@@ -1114,20 +1152,36 @@ class LlamaForCausalLM(nn.Module):
             self.lm_head_p = gemm.pack_weight(self.lm_head)
         # the prefill path's widen scratch: one buffer the size of the largest projection, owned by
         # the model and shared by its handles (fixed address for the model's lifetime)
-        self._w8_scratch = torch.empty(largest, dtype=torch.bfloat16, device=self.device) if cuda else None
+        self._widen_scratch = torch.empty(largest, dtype=torch.bfloat16, device=self.device) if cuda else None
         for layer in self.layers:
             for h in (layer.attn.qkv_p, layer.attn.o_p, layer.mlp.gate_up_p, layer.mlp.down_p):
-                h.scratch = self._w8_scratch
-        self.w8 = True
+                h.scratch = self._widen_scratch
+        self.quantised_dtype = wd
+        self.w8 = q is gemm_w8
         self.packed_only = True
         self._ones_h = torch.ones(self.cfg.hidden_size, dtype=self.lm_head.dtype, device=self.device)
         logging.getLogger(__name__).info(
-            "weights: dtype fp8 (e4m3, per-channel scales), %d projection bytes, %d widen-scratch bytes",
-            self.projection_bytes(), self.w8_scratch_bytes())
+            "weights: dtype %s, %d projection bytes, %d widen-scratch bytes",
+            label, self.projection_bytes(), self.widen_scratch_bytes())
         return True
 
+    @property
+    def wq(self):
+        """The ops module of the quantised projection handles (gemm_w8 / gemm_w4); None: not quantised."""
+        return QUANT_FORMATS[self.quantised_dtype].ops if self.quantised_dtype is not None else None
+
+    @property
+    def _w8_scratch(self):
+        """The widen scratch under the name it had when FP8 was the only quantised format."""
+        return getattr(self, "_widen_scratch", None)
+
     def w8_scratch_bytes(self) -> int:
-        t = getattr(self, "_w8_scratch", None)
+        """:meth:`widen_scratch_bytes` under its earlier name."""
+        return self.widen_scratch_bytes()
+
+    def widen_scratch_bytes(self) -> int:
+        """Bytes of the wide path's widen scratch (shared by the quantised handles of either format)."""
+        t = getattr(self, "_widen_scratch", None)
         return 0 if t is None else t.numel() * t.element_size()
 
     def projection_bytes(self) -> int:
@@ -1138,7 +1192,8 @@ class LlamaForCausalLM(nn.Module):
         for layer in self.layers:
             for owner in (layer.attn, layer.mlp):
                 for v in list(vars(owner).values()) + list(owner._parameters.values()):
-                    tensors = (v.packed, v.scale) if isinstance(v, gemm_w8.W8) else (v,)
+                    tensors = ((v.packed, v.scale) if isinstance(v, gemm_w8.W8) else
+                               (v.packed, v.scales) if isinstance(v, gemm_w4.W4) else (v,))
                     for t in tensors:
                         if isinstance(t, torch.Tensor) and not t.is_meta and (t.dim() >= 2 or t is not v):
                             held[t.data_ptr()] = t.numel() * t.element_size()

@@ -82,6 +82,9 @@ SIGNATURES = {
     "pk_w8_gemm": [P, P, P, P, P, I32, I32, I32, I32, I32, I32, I32, P, I32, F32, P],
     "pk_w8_widen": [P, P, I32, I32, P],
     "pk_col_scale": [P, P, I32, I32, I32, P],
+    # weight-only MXFP4 projections (csrc/kernels/gemm_w4.hip)
+    "pk_w4_gemm": [P, P, P, P, P, I32, I32, I32, I32, I32, I32, I32, P, I32, F32, P],
+    "pk_w4_widen": [P, P, P, I32, I32, P],
     # multi-LoRA shrink / expand (csrc/kernels/lora.hip)
     "pk_lora_shrink": [P, P, I64, P, P, P, I32, I32, I32, I32, I32, P, I32, F32, P],
     "pk_lora_expand": [P, I64, I32, P, P, P, P, P, I32, I32, I32, I32, I32, I32, I32, I32, P],

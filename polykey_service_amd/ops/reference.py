@@ -188,6 +188,66 @@ def w8_linear_f64(x, b, scale, rinv=None) -> torch.Tensor:
     return w8_linear(x, b, scale, rinv, dtype=torch.float64)
 
 
+# MXFP4 (OCP Microscaling v1.0): e2m1 elements, one e8m0 scale byte per block of 32 along K
+E2M1_VALUES = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0, -0.0, -0.5, -1.0, -1.5, -2.0, -3.0, -4.0, -6.0)
+MX_BLOCK = 32
+MX_SCALE_MIN, MX_SCALE_MAX = 2, 252  # scale bytes for which every e2m1 * 2^(X - 127) is a normal bf16 (or 0)
+# twice the magnitude (0, 1, 2, 3, 4, 6, 8, 12) -> e2m1 code
+_E2M1_CODE = (0, 1, 2, 3, 4, -1, 5, -1, 6, -1, -1, -1, 7)
+
+
+def quantize_mxfp4_rows(w: torch.Tensor):
+    """Weight-only MXFP4 of a ``[N, K]`` projection (K % 32 == 0), the OCP MX v1.0 rule per block of
+    32 along K: ``X = clamp(floor(log2(amax)) - 2 + 127, 2, 252)`` (an all-zero block: 127), elements
+    ``w / 2^(X - 127)`` rounded to the nearest e2m1 value with ties to even and saturated at +-6
+    (quotients in (6, 8) saturate: the standard's behaviour).  Returns (nibbles ``[N, K / 2]`` uint8,
+    low nibble = even k; scales ``[N, K / 32]`` uint8): the interchange layout.
+
+    The quotient is formed in float64, where a division by a power of two is exact."""
+    N, K = w.shape
+    assert K % MX_BLOCK == 0, f"MXFP4 needs K % 32 == 0 (got {K})"
+    nib = torch.empty((N, K // 2), dtype=torch.uint8, device=w.device)
+    xs = torch.empty((N, K // MX_BLOCK), dtype=torch.uint8, device=w.device)
+    code_of = torch.tensor(_E2M1_CODE, dtype=torch.int64, device=w.device)
+    rows = 2048  # bounds the float64 temporary of a large projection
+    for r in range(0, N, rows):
+        v = w[r:r + rows].double().view(-1, K // MX_BLOCK, MX_BLOCK)
+        amax = v.abs().amax(dim=-1)
+        # floor(log2(amax)) is the float64 exponent field (bit operations: the same on every device)
+        e = ((amax.view(torch.int64) >> 52) & 0x7FF) - 1023
+        X = torch.where(amax > 0, (e - 2 + 127).clamp(MX_SCALE_MIN, MX_SCALE_MAX), torch.full_like(e, 127))
+        q = v * ((1023 + 127 - X) << 52).view(torch.float64)[..., None]  # times 2^(127 - X), as float64 bits
+        a = q.abs()
+        # round to nearest even on a grid of step 0.5 below 2, 1 below 4, 2 above: torch.round is
+        # half-to-even, and an even multiple of the step is an even e2m1 code
+        m = torch.where(a < 2, torch.round(a * 2) / 2, torch.where(a < 4, torch.round(a), torch.round(a / 2) * 2))
+        code = code_of[(m.clamp(max=6.0) * 2).long()]
+        code = torch.where((q < 0) & (code > 0), code + 8, code).view(-1, K // 2, 2)
+        nib[r:r + rows] = (code[..., 0] | (code[..., 1] << 4)).to(torch.uint8)
+        xs[r:r + rows] = X.to(torch.uint8)
+    return nib, xs
+
+
+def dequantize_mxfp4(nib: torch.Tensor, xs: torch.Tensor, dtype=torch.float32) -> torch.Tensor:
+    """``[N, K]`` values of MXFP4 nibbles ``[N, K / 2]`` and scale bytes ``[N, K / 32]``:
+    ``E2M1[nibble] * 2^(X - 127)``, exact in fp32 for X in [2, 252]."""
+    N, K = nib.shape[0], nib.shape[1] * 2
+    table = torch.tensor(E2M1_VALUES, dtype=torch.float32, device=nib.device)
+    n = nib.long()
+    v = table[torch.stack([n & 15, n >> 4], dim=-1).view(N, K)]
+    scale = (xs.to(torch.int32) << 23).view(torch.float32)  # 2^(X - 127) as fp32 bits
+    return (v.view(N, K // MX_BLOCK, MX_BLOCK) * scale[..., None]).view(N, K).to(dtype)
+
+
+def w4_linear(x: torch.Tensor, nib: torch.Tensor, xs: torch.Tensor, rinv: Optional[torch.Tensor] = None,
+              dtype=torch.float32) -> torch.Tensor:
+    """The function every W4 projection computes, before its epilogue's rounding:
+    ``y[m, n] = sum_k x[m, k] * E2M1[nib[n, k]] * 2^(X[n, k / 32] - 127)`` (times ``rinv[m]`` with the
+    folded norm), products and sums in ``dtype`` (fp32: the ops' CPU path; float64: the tests')."""
+    y = x.to(dtype) @ dequantize_mxfp4(nib, xs, dtype).t()
+    return y if rinv is None else y * rinv.to(dtype)[:, None]
+
+
 def _store(cache_flat: torch.Tensor, index: tuple, rows: torch.Tensor, scale: float) -> None:
     """cache_flat[index] = rows in the cache's dtype (FP8 caches: quantised, indexed as bytes)."""
     if cache_flat.dtype == FP8:

@@ -37,7 +37,7 @@ class Metrics:
         self.kv_bytes_per_token = Gauge("polykey_engine_kv_cache_bytes_per_token", "KV-cache bytes one token takes "
                                         "on this rank (all layers, K and V): halves with an FP8 cache", registry=r)
         self.weight_bytes = Gauge("polykey_engine_weight_bytes", "bytes of the decoder layers' projection weights "
-                                  "on this rank: halves with weight_dtype=fp8", registry=r)
+                                  "on this rank: halves with weight_dtype=fp8, 4.25 / 16 with mxfp4", registry=r)
         self.lora_bytes = Gauge("polykey_engine_lora_bytes", "bytes of the resident LoRA adapters: slots x max rank "
                                 "x sum over projections of (K + N) x 2 x layers; 0 without adapters", registry=r)
         self.step_seconds = Histogram("polykey_engine_step_seconds", "engine step wall time", buckets=_TOK_BUCKETS,
