@@ -46,6 +46,21 @@ __global__ void __launch_bounds__(64 * NW) paged_decode_kernel(
                                                  blockIdx.x, blockIdx.y, blockIdx.z, gridDim.z, lds, Flow{}, sc...);
 }
 
+// A verify step of speculative decoding: decode_tile with (row, head) columns (attn_decode.h
+// VerifyIn).  Same grid, block and LDS as paged_decode_kernel; q given, bf16 cache.
+template <int kPart, int NW>
+__global__ void __launch_bounds__(64 * NW) paged_verify_kernel(
+    bf16_t* __restrict__ out, const bf16_t* __restrict__ q, bf16_t* __restrict__ kc, bf16_t* __restrict__ vc,
+    const int* __restrict__ block_tables, const int* __restrict__ context_lens, float* __restrict__ part_o,
+    float* __restrict__ part_ml, int n_q, int n_kv, int bs, int max_blocks, int q_stride, int out_stride,
+    int n_parts, float scale2, const VerifyIn vi) {
+  __shared__ DecodeLds<kPart, NW> lds;
+  decode_tile<kPart, NW, false, 0, 0, 0, bf16_t, true>(out, q, kc, vc, block_tables, context_lens, part_o, part_ml,
+                                                       n_q, n_kv, bs, max_blocks, q_stride, out_stride, n_parts,
+                                                       scale2, QkvIn{}, blockIdx.x, blockIdx.y, blockIdx.z, gridDim.z,
+                                                       lds, Flow{}, KvScale{}, vi);
+}
+
 // ----------------------------------------------------------------------------- prefill
 // grid (max_q_blocks, n_seqs, n_kv * head_groups), block 64*W with W = min(G, 8) waves:
 // wave w = query head h*G + sub*W + w, 16 query tokens per workgroup.  cu_q: query offsets
@@ -461,6 +476,36 @@ PK_EXPORT int pk_paged_decode_qkv(void* out, const void* partial, int S, int M, 
                  static_cast<const float*>(cos_sin), static_cast<const int*>(slots), S, M};
   return decode_launch(out, nullptr, qi, k_cache, v_cache, block_tables, context_lens, part_o, part_ml, n_seqs, n_q,
                        n_kv, bs, max_blocks, 0, out_stride, scale, max_ctx, kv_dtype, k_scale, v_scale, stream);
+}
+
+// Verify step of speculative decoding (attn_decode.h VerifyIn): q / out hold n_seqs * qr rows,
+// sequence s owning rows s * qr .. s * qr + qr - 1, of which the first n_rows[s] (1..qr, checked by
+// the caller) are real; context_lens[s] counts the cached keys including those n_rows[s].  Row j
+// attends keys 0 .. context_lens[s] - n_rows[s] + j; the other rows, and every row of a sequence
+// with no context, are written as zeros.  The launch plan is the decode plan of n_seqs sequences,
+// the partial slabs hold n_seqs * qr rows of n_q heads, and the merge sees one sequence's qr rows
+// as qr * n_q heads, which is why `out` rows must be contiguous (out_stride == n_q * 128).
+// -1: an FP8 cache, qr < 1, qr * G > 16, strided out rows.
+PK_EXPORT int pk_paged_verify(void* out, const void* q, const void* k_cache, const void* v_cache,
+                              const void* block_tables, const void* context_lens, const void* n_rows, void* part_o,
+                              void* part_ml, int n_seqs, int qr, int n_q, int n_kv, int bs, int max_blocks,
+                              int q_stride, int out_stride, float scale, int max_ctx, int kv_dtype,
+                              hipStream_t stream) {
+  if (kv_dtype != 0 || qr < 1 || n_kv <= 0 || n_q % n_kv || qr * (n_q / n_kv) > 16 || out_stride != n_q * kHD ||
+      n_rows == nullptr)
+    return -1;
+  if (n_seqs <= 0) return 0;
+  DecodePlan plan;
+  if (const int rc = decode_plan(plan, n_seqs, n_q, n_kv, bs, max_blocks, max_ctx, part_o, part_ml)) return rc;
+  const auto kernel = plan.part == kDecodePartSmall ? &paged_verify_kernel<kDecodePartSmall, kDecodeWaves>
+                                                    : &paged_verify_kernel<kDecodePart, kDecodeWaves>;
+  kernel<<<dim3(n_kv, n_seqs, plan.z), 64 * kDecodeWaves, 0, stream>>>(
+      static_cast<bf16_t*>(out), static_cast<const bf16_t*>(q), static_cast<bf16_t*>(const_cast<void*>(k_cache)),
+      static_cast<bf16_t*>(const_cast<void*>(v_cache)), static_cast<const int*>(block_tables),
+      static_cast<const int*>(context_lens), static_cast<float*>(part_o), static_cast<float*>(part_ml), n_q, n_kv, bs,
+      max_blocks, q_stride, out_stride, plan.n_parts, scale * kLog2e, VerifyIn{static_cast<const int*>(n_rows), qr});
+  const int rc = PK_CHECK_LAUNCH();
+  return rc ? rc : decode_merge(plan, out, part_o, part_ml, context_lens, n_seqs, n_q * qr, out_stride * qr, stream);
 }
 
 // CT: cache element type; v_scale: none (bf16) or the V scale (FP8, `scale` then carries the K scale)

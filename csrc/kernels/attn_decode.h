@@ -256,6 +256,21 @@ struct QkvIn {
   int S, M;
 };
 
+// A verify step (speculative decoding, VQ): sequence `seq` owns `qr` consecutive query rows
+// seq * qr + j, of which the first n_rows[seq] = R (1..qr) are real.  Column c = j * G + head of the
+// 16-column tile holds row j's query for q head h * G + head (qr * G <= 16: the columns a plain
+// decode launch leaves as padding).  context_lens[seq] = C counts the keys in the cache including
+// the R written this step; row j < R attends keys 0 .. C - R + j, rows j >= R come out as zeros.
+struct VerifyIn {
+  const int* n_rows = nullptr;  // [n_seqs]
+  int qr = 1;
+};
+
+// where column c = j * G + head of a verify tile writes: head h * G + head of row seq * qr + j
+__device__ __forceinline__ int64_t verify_out(int c, int seq, int h, int G, int qr, int out_stride) {
+  return (static_cast<int64_t>(seq) * qr + c / G) * out_stride + (h * G + c % G) * kHD;
+}
+
 // LDS of one decode-attention workgroup (passed in: a fused launch shares it with its GEMM tiles)
 template <int kPart, int NW>
 struct DecodeLds {
@@ -278,14 +293,21 @@ struct DecodeLds {
 // new token's k / v are quantised as the cache stores them (kn_s / vn_s hold the widened bytes, so
 // the fold path attends to exactly what a later step reads back), and the V scale multiplies the
 // result once, where it is normalised or handed to the merge kernel.
-template <int kPart, int NW, bool FROM_QKV, int SS = 0, int FL = 0, int PRE = 0, typename CT = bf16_t>
+// (The VQ branches below are written next to the plain statements, not folded into them: the decode
+// and fused kernels then compile to the device code they had before VQ existed.)
+// VQ (q given, bf16 cache): a verify step, see VerifyIn.  The tile's columns are (row, head) pairs,
+// each with its own causal limit; `out`, `q` and the partial slabs are indexed by row seq * qr + j
+// (the slabs as [n_seqs * qr, n_q, n_parts]: decode_merge is launched over n_q * qr "heads").
+template <int kPart, int NW, bool FROM_QKV, int SS = 0, int FL = 0, int PRE = 0, typename CT = bf16_t, bool VQ = false>
 __device__ __forceinline__ void decode_tile(
     bf16_t* __restrict__ out, const bf16_t* __restrict__ q, CT* __restrict__ kc,
     CT* __restrict__ vc, const int* __restrict__ block_tables, const int* __restrict__ context_lens,
     float* __restrict__ part_o, float* __restrict__ part_ml, int n_q, int n_kv, int bs,
     int max_blocks, int q_stride, int out_stride, int n_parts, float scale2, const QkvIn qi, const int bx,
-    const int by, const int bz, const int gdz, DecodeLds<kPart, NW>& L, const Flow& fin, const KvScale ks = KvScale{}) {
+    const int by, const int bz, const int gdz, DecodeLds<kPart, NW>& L, const Flow& fin, const KvScale ks = KvScale{},
+    const VerifyIn vi = VerifyIn{}) {
   constexpr bool kFp8 = kIsFp8<CT>;
+  static_assert(!VQ || (!FROM_QKV && !kFp8 && PRE == 0 && FL == 0), "verify: q given, bf16 cache, stand-alone launch");
   auto& o_lds = L.o_lds;
   auto& ml_lds = L.ml_lds;
   auto& bt_s = L.bt_s;
@@ -317,6 +339,7 @@ __device__ __forceinline__ void decode_tile(
   int ctx = ld_vmem(context_lens + seq);
   int pos_q = FROM_QKV ? ld_vmem(qi.positions + seq) : 0;
   int slot_q = FROM_QKV ? ld_vmem(qi.slots + seq) : -1;
+  int n_rows = VQ ? ld_vmem(vi.n_rows + seq) : 1;
   // (entries of the block-table window past the sequence's blocks are in-bounds of the row and
   // never used)
   const int pre_b0 = static_cast<int>(bz) * (kPart / bs);
@@ -340,6 +363,7 @@ __device__ __forceinline__ void decode_tile(
   // the three scalars are needed from here on: their wait (issued first) leaves the slab loads in
   // flight, and the memory clobber keeps the slab loads above it
   asm volatile("" : "+v"(ctx), "+v"(pos_q), "+v"(slot_q) :: "memory");
+  if constexpr (VQ) asm volatile("" : "+v"(n_rows));
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int64_t blk_stride = static_cast<int64_t>(n_kv) * bs * kHD;
   const CT* kch = kc + static_cast<int64_t>(h) * bs * kHD;
@@ -370,9 +394,15 @@ __device__ __forceinline__ void decode_tile(
   if constexpr ((FL & 2) != 0) flow_wait(fin, h);  // this kv head's QKV tiles (every workgroup: re-arm count)
   const int G = n_q / n_kv;
   if (ctx <= 0) {
-    if (bz == 0)  // a padded (graph) row -> zeros
-      for (int idx = threadIdx.x; idx < G * kHD; idx += 64 * NW)
-        out[static_cast<int64_t>(seq) * out_stride + (h * G + idx / kHD) * kHD + idx % kHD] = 0;
+    if (bz == 0) {  // a padded (graph) row -> zeros
+      if constexpr (VQ) {  // all qr rows of the sequence
+        for (int idx = threadIdx.x; idx < vi.qr * n_q / n_kv * kHD; idx += 64 * NW)
+          out[verify_out(idx / kHD, seq, h, n_q / n_kv, vi.qr, out_stride) + idx % kHD] = 0;
+      } else {
+        for (int idx = threadIdx.x; idx < G * kHD; idx += 64 * NW)
+          out[static_cast<int64_t>(seq) * out_stride + (h * G + idx / kHD) * kHD + idx % kHD] = 0;
+      }
+    }
     return;
   }
   // n_parts comes from the launch's context bound; the clamp keeps a violated bound in-bounds
@@ -517,9 +547,17 @@ __device__ __forceinline__ void decode_tile(
       for (int o = 8; o > 0; o >>= 1) sdot += __shfl_xor(sdot, o, 64);
       if (c < G && part == 0) sn_s[c] = sdot * scale2;
     }
+  } else if constexpr (VQ) {
+    const int j = min(r / G, vi.qr - 1);  // (columns past qr * G: an in-bounds address, never loaded)
+    load_q(qf, q + (static_cast<int64_t>(seq) * vi.qr + j) * q_stride + (h * G + r % G) * kHD,
+           r / G < min(n_rows, vi.qr));
   } else {
     load_q(qf, q + static_cast<int64_t>(seq) * q_stride + (h * G + r) * kHD, r < G);
   }
+  // the last key this lane's column attends: every cached key, or (VQ) row j's causal limit
+  // C - R + j -- no key at all for the padding rows j >= R, whose l stays 0 and output becomes 0
+  int col_limit = 0;
+  if constexpr (VQ) col_limit = r / G < min(n_rows, vi.qr) ? ctx - n_rows + r / G : -1;
 
   // the grid's z dimension is small (<= 4); a workgroup walks partitions z, z + gdz, ...
   // carrying its online-softmax state across them (the order of key blocks does not matter to
@@ -553,8 +591,13 @@ __device__ __forceinline__ void decode_tile(
             load_kv(fb, kch, vch, blk_stride, bt_s, b0, bs, begin + kStep * w + NW * kStep, min(ctx_c, end));
         }
       }
-      attend<PRE>(st, qf, kch, vch, blk_stride, bt_s, b0, bs, begin + kStep * w, end, NW * kStep, ctx_c, ctx_c - 1,
-                  scale2, fa, fb);
+      if constexpr (VQ) {
+        attend<PRE>(st, qf, kch, vch, blk_stride, bt_s, b0, bs, begin + kStep * w, end, NW * kStep, ctx_c, col_limit,
+                    scale2, fa, fb);
+      } else {
+        attend<PRE>(st, qf, kch, vch, blk_stride, bt_s, b0, bs, begin + kStep * w, end, NW * kStep, ctx_c, ctx_c - 1,
+                    scale2, fa, fb);
+      }
     }
   }
   const float lsum = col_sum(st.l);
@@ -567,7 +610,7 @@ __device__ __forceinline__ void decode_tile(
     ml_lds[w][r][1] = lsum;
   }
   __syncthreads();
-  for (int idx = threadIdx.x; idx < G * kHD; idx += 64 * NW) {
+  for (int idx = threadIdx.x; idx < (VQ ? vi.qr * G : G) * kHD; idx += 64 * NW) {
     const int c = idx / kHD, d = idx % kHD;
     float M = kNegBig;
 #pragma unroll
@@ -589,9 +632,14 @@ __device__ __forceinline__ void decode_tile(
     const int hq = h * G + c;
     if constexpr (kFp8) O *= ks.v;  // V scale: once per output element, ahead of 1 / l or the merge
     if (n_eff == 1) {
-      out[static_cast<int64_t>(seq) * out_stride + hq * kHD + d] = f2bf(L > 0.f ? O / L : 0.f);
+      if constexpr (VQ)
+        out[verify_out(c, seq, h, G, vi.qr, out_stride) + d] = f2bf(L > 0.f ? O / L : 0.f);
+      else
+        out[static_cast<int64_t>(seq) * out_stride + hq * kHD + d] = f2bf(L > 0.f ? O / L : 0.f);
     } else {
-      const int64_t pi = (static_cast<int64_t>(seq) * n_q + hq) * n_parts + bz;
+      // (VQ: slab row = query row, [n_seqs * qr, n_q, n_parts])
+      const int64_t pi = VQ ? ((static_cast<int64_t>(seq) * vi.qr + c / G) * n_q + h * G + c % G) * n_parts + bz
+                            : (static_cast<int64_t>(seq) * n_q + hq) * n_parts + bz;
       part_o[pi * kHD + d] = O;
       if (d == 0) {
         part_ml[2 * pi] = M;

@@ -47,7 +47,7 @@ from ..service.tool_calls import run_chat, tool_rounds, validate_tools
 
 _SAMPLING_KEYS = ("max_tokens", "temperature", "top_p", "top_k", "min_p", "seed", "stop", "ignore_eos",
                   "stop_token_ids", "cache_salt", "repetition_penalty", "frequency_penalty", "presence_penalty",
-                  "logit_bias", "guided_regex", "guided_choice", "guided_json")
+                  "logit_bias", "guided_regex", "guided_choice", "guided_json", "speculative")
 
 
 

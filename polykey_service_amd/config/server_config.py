@@ -47,6 +47,12 @@ class ServerConfig:
     # resident; OpenAI "model": "<name>" / "llm.chat:<name>" / parameters.lora pick one
     lora_modules: str = ""
     max_lora_rank: int = 64
+    # speculative decoding: "" = off, "ngram" = prompt-lookup drafts verified in one step (dense
+    # models, one GPU, bf16 KV cache); k draft tokens per sequence and step, n-gram lengths tried
+    speculative: str = ""
+    num_speculative_tokens: int = 3
+    ngram_max: int = 4
+    ngram_min: int = 2
     hip_graphs: bool = True
     device: str = "cuda"
     seed: int = 0
@@ -85,6 +91,10 @@ _ENV = {
     "weight_dtype": "POLYKEY_WEIGHT_DTYPE",
     "lora_modules": "POLYKEY_LORA_MODULES",
     "max_lora_rank": "POLYKEY_MAX_LORA_RANK",
+    "speculative": "POLYKEY_SPECULATIVE",
+    "num_speculative_tokens": "POLYKEY_NUM_SPECULATIVE_TOKENS",
+    "ngram_max": "POLYKEY_NGRAM_MAX",
+    "ngram_min": "POLYKEY_NGRAM_MIN",
     "hip_graphs": "POLYKEY_HIP_GRAPHS",
     "device": "POLYKEY_DEVICE",
     "seed": "POLYKEY_SEED",
@@ -130,6 +140,19 @@ def env_weight_dtype(environ: Optional[Mapping[str, str]] = None) -> str:
     """The weight dtype a config built without the field takes: ``POLYKEY_WEIGHT_DTYPE`` (the
     variable of :data:`_ENV`), else "auto".  Explicit values always win."""
     return (os.environ if environ is None else environ).get(_ENV["weight_dtype"], "") or "auto"
+
+
+SPECULATIVE_METHODS = ("ngram",)
+
+
+def normalize_speculative(value) -> str:
+    """``--speculative`` / ``POLYKEY_SPECULATIVE`` -> "" (off) or "ngram"; anything else is an error."""
+    v = str(value or "").strip().lower()
+    if v in ("", "none", "off"):
+        return ""
+    if v in SPECULATIVE_METHODS:
+        return v
+    raise ValueError(f"speculative must be one of {', '.join(SPECULATIVE_METHODS)} (got {value!r})")
 
 
 def parse_lora_modules(spec) -> tuple:
@@ -191,4 +214,8 @@ def load_server_config(argv: Optional[Sequence[str]] = None,
     cfg.kv_cache_dtype = normalize_kv_cache_dtype(cfg.kv_cache_dtype)
     cfg.weight_dtype = normalize_weight_dtype(cfg.weight_dtype)
     parse_lora_modules(cfg.lora_modules)  # a malformed list fails at start-up
+    cfg.speculative = normalize_speculative(cfg.speculative)
+    if cfg.speculative and (cfg.num_speculative_tokens < 1 or not 1 <= cfg.ngram_min <= cfg.ngram_max):
+        raise ValueError("speculative decoding needs num_speculative_tokens >= 1 and 1 <= ngram_min <= ngram_max "
+                         f"(got {cfg.num_speculative_tokens}, {cfg.ngram_min}, {cfg.ngram_max})")
     return cfg

@@ -23,7 +23,7 @@ from ..models.config import ModelConfig, get_config
 from ..models.llama import QUANT_FORMATS
 from ..ops.sampler import logprob_entry
 from ..parallel.state import ParallelState, get_state
-from . import grammar
+from . import grammar, spec
 from .model_runner import ModelRunner, RunnerConfig
 from .scheduler import ScheduledBatch, Scheduler
 from .sequence import FinishReason, RequestOutput, SamplingParams, Sequence, seq_metrics
@@ -73,6 +73,12 @@ class EngineConfig:
     # "LoRA adapters"); a request picks one with SamplingParams.lora.  () = off: nothing changes
     lora_modules: tuple = ()
     max_lora_rank: int = 64
+    # speculative decoding (README "Speculative decoding"): None = off, "ngram" = prompt-lookup drafts
+    # verified in one step; num_speculative_tokens = k drafts per sequence and step (k + 1 query rows)
+    speculative: Optional[str] = None
+    num_speculative_tokens: int = 3
+    ngram_max: int = 4
+    ngram_min: int = 2
 
     @classmethod
     def from_server_config(cls, sc) -> "EngineConfig":
@@ -83,7 +89,10 @@ class EngineConfig:
                    num_layers=getattr(sc, "num_layers", 0), kv_cache_dtype=getattr(sc, "kv_cache_dtype", "auto"),
                    weight_dtype=getattr(sc, "weight_dtype", "auto"),
                    lora_modules=parse_lora_modules(getattr(sc, "lora_modules", "")),
-                   max_lora_rank=getattr(sc, "max_lora_rank", 64))
+                   max_lora_rank=getattr(sc, "max_lora_rank", 64),
+                   speculative=getattr(sc, "speculative", "") or None,
+                   num_speculative_tokens=getattr(sc, "num_speculative_tokens", 3),
+                   ngram_max=getattr(sc, "ngram_max", 4), ngram_min=getattr(sc, "ngram_min", 2))
 
 
 def tokenizer_for(cfg: EngineConfig, mcfg: Optional[ModelConfig] = None):
@@ -131,6 +140,8 @@ class LLMEngine:
                 raise ValueError(f"LoRA adapters do not support weight_dtype={wd} yet: the "
                                  f"{'W8' if wd == 'fp8' else 'W4'} chain has no "
                                  "adapter path (a follow-up; use weight_dtype=bf16)")
+        if cfg.speculative:
+            self._check_speculative(cfg, mcfg)
         if cfg.num_layers > 0 and cfg.num_layers != mcfg.num_layers:
             mcfg = dataclasses.replace(mcfg, num_layers=cfg.num_layers)
         if cfg.max_model_len > mcfg.max_position:
@@ -201,7 +212,8 @@ class LLMEngine:
                             max_num_batched_tokens=cfg.max_num_batched_tokens, max_model_len=cfg.max_model_len,
                             num_kv_blocks=cfg.num_kv_blocks, gpu_mem_fraction=cfg.gpu_mem_fraction,
                             hip_graphs=cfg.hip_graphs, graph_batch_sizes=tuple(cfg.graph_batch_sizes),
-                            kv_cache_dtype=cfg.kv_cache_dtype)
+                            kv_cache_dtype=cfg.kv_cache_dtype,
+                            spec_qr=cfg.num_speculative_tokens + 1 if cfg.speculative else 0)
         self.runner = ModelRunner(model, rcfg, dev)
         # guided decoding: the byte string of every vocabulary id, built once and kept on the device
         off, data = grammar.token_bytes(self.tokenizer, mcfg.vocab_size)
@@ -233,6 +245,45 @@ class LLMEngine:
         # that arrived meanwhile)
         self.before_schedule: Optional[Callable[[], None]] = None
         self.continuation_steps = 0
+        # speculative decoding: the proposer (a plain attribute: tests install scripted ones), and
+        # counters of verify steps, draft tokens fed to them and draft tokens accepted
+        self.proposer: Optional[spec.Proposer] = None
+        self.spec_k = 0
+        self.spec_steps = self.spec_draft_tokens = self.spec_accepted_tokens = 0
+        if cfg.speculative:
+            self.spec_k = cfg.num_speculative_tokens
+            self.proposer = spec.NgramProposer(cfg.ngram_max, cfg.ngram_min)
+            logging.getLogger(__name__).info(
+                "speculative decoding: method %s, k %d, QR %d, verify graph buckets %s", cfg.speculative, self.spec_k,
+                self.spec_k + 1, sorted(self.runner.verify_graphs) or "none (eager)")
+
+    def _check_speculative(self, cfg: "EngineConfig", mcfg: ModelConfig) -> None:
+        """What speculative decoding covers: dense Llama / Qwen3 on one GPU with a bf16 KV cache and
+        k + 1 query rows that fit the verify attention's 16-column tile.  No silent fallback."""
+        opt = f"speculative={cfg.speculative}"
+        if cfg.speculative not in spec.METHODS:
+            raise ValueError(f"speculative must be one of {', '.join(spec.METHODS)} (got {cfg.speculative!r})")
+        if mcfg.is_moe:
+            raise ValueError(f"{opt} does not support MoE models ({mcfg.name})")
+        if self.st.tp_size > 1:
+            raise ValueError(f"{opt} does not support tp={self.st.tp_size}")
+        if self.st.ep_size > 1 or self.st.dp_attention:
+            raise ValueError(f"{opt} does not support ep={self.st.ep_size} / DP attention")
+        if cfg.lora_modules:
+            raise ValueError(f"{opt} does not support LoRA adapters (lora_modules)")
+        if cfg.kv_cache_dtype == "fp8":
+            raise ValueError(f"{opt} does not support kv_cache_dtype=fp8: the verify attention reads a bf16 cache")
+        k = cfg.num_speculative_tokens
+        group = mcfg.num_heads // mcfg.num_kv_heads
+        k_max = spec.max_draft_tokens(group)
+        if isinstance(k, bool) or not isinstance(k, int) or k < 1:
+            raise ValueError(f"num_speculative_tokens must be an integer >= 1 (got {k!r})")
+        if k > k_max:
+            raise ValueError(f"num_speculative_tokens={k} does not fit {mcfg.name}: (k + 1) x {group} query heads per "
+                             f"kv head exceed the verify attention's {spec.VERIFY_COLUMNS} columns; the largest k for "
+                             f"this model is {k_max}")
+        if not 1 <= cfg.ngram_min <= cfg.ngram_max:
+            raise ValueError(f"ngram_min / ngram_max must satisfy 1 <= min <= max (got {cfg.ngram_min}, {cfg.ngram_max})")
 
     def _load_adapters(self, model, mcfg: ModelConfig) -> None:
         from ..models.lora import MAX_SLOTS, LoraAdapter
@@ -285,6 +336,8 @@ class LLMEngine:
                              f"{', '.join(self.lora_names) if self.lora_names else 'no adapters'}")
         g = self._grammar(params)
         seq = Sequence(request_id or uuid.uuid4().hex, prompt_ids, params, self.mcfg.eos_token_id, user)
+        if self.spec_k:
+            seq.spec_drafted = seq.spec_accepted = 0
         if g is None:
             self.scheduler.add(seq)
             return seq
@@ -360,6 +413,8 @@ class LLMEngine:
             # a step is in flight does)
             done = [d for d in done if d[2] is not None or d[0].finish_reason is not FinishReason.ABORT]
         batch = self.scheduler.schedule()
+        if self.spec_k:
+            self._propose(batch)
         if not batch.empty:
             sampling = batch.sampling_seqs()
             self._inflight = (batch, sampling, self.runner.launch(batch))
@@ -430,6 +485,8 @@ class LLMEngine:
         (see ModelRunner.launch_continuation) when nothing else could change the batch: pure
         decode, every running sequence in it and alive, no request waiting for admission."""
         sch = self.scheduler
+        if self.spec_k:  # the proposer needs the sampled tokens on the host before the next step is packed
+            return None
         if (not self.overlap or batch.prefills or sch.waiting or len(batch.decodes) != len(sch.running)
                 or any(s.is_finished() for s in batch.decodes)):
             return None
@@ -437,7 +494,72 @@ class LLMEngine:
             return None  # the in-flight step ends every sequence: a continuation would be discarded
         return self.runner.launch_continuation(batch, handle)
 
+    def _propose(self, batch: ScheduledBatch) -> None:
+        """After ``schedule()`` returned a pure-decode batch: ask the proposer for every sequence that
+        may speculate and reserve KV for the drafts.  With at least one draft the batch becomes a
+        verify step (``batch.drafts``); otherwise -- no draft, prefill in the batch, more rows than a
+        decode step may have -- it stays today's step.  Drafts are clipped to k, to the tokens the
+        request may still emit after this step's own, to the model length, and to what the KV pool
+        grants: dropped one by one, never preempting anyone."""
+        seqs = batch.decodes
+        if batch.prefills or not seqs or len(seqs) > self.runner.verify_max_seqs:
+            return
+        k, bm, any_draft = self.spec_k, self.bm, False
+        drafts: List[List[int]] = []
+        for s in seqs:
+            p = s.params
+            room = min(k, p.max_tokens - len(s.output_ids) - 1, self.cfg.max_model_len - s.num_tokens - 1)
+            d: List[int] = []
+            if room > 0 and p.speculative is not False and not p.has_penalties and s.grammar is None:
+                d = list(self.proposer.propose(s, room))[:room]
+                while d and not bm.allocate(s.seq_id, s.num_computed + 1 + len(d)):
+                    d.pop()
+            drafts.append(d)
+            any_draft = any_draft or bool(d)
+        if any_draft:
+            batch.drafts = drafts
+
+    def _complete_verify(self, batch, handle):
+        """A verify step read back.  Sequence i sampled rows ``i * QR + j``; ``n_acc`` is the number of
+        leading drafts that equal the sample of the row before them, and the sequence emits samples
+        ``0 .. n_acc`` -- one token at a time, stopping at the first finish reason -- and advances by
+        ``1 + n_acc`` computed positions (the KV of rejected drafts lies beyond and is overwritten)."""
+        toks = self.runner.fetch(handle)
+        lp_rows = self.runner.fetch_logprobs(handle) if len(handle) > 4 and handle[4] is not None else None
+        now = time.monotonic()
+        qr = self.spec_k + 1
+        done = []
+        self.spec_steps += 1
+        for i, (s, d) in enumerate(zip(batch.decodes, batch.drafts)):
+            if s.is_finished():  # aborted while its step was in flight
+                continue
+            row = toks[i * qr:i * qr + 1 + len(d)]
+            n_acc = 0
+            while n_acc < len(d) and row[n_acc] == d[n_acc]:
+                n_acc += 1
+            s.num_computed += 1 + n_acc
+            s.spec_drafted += len(d)
+            s.spec_accepted += n_acc
+            self.spec_draft_tokens += len(d)
+            self.spec_accepted_tokens += n_acc
+            emitted, reason = [], None
+            for j in range(n_acc + 1):
+                if s.logprobs is not None:
+                    s.logprobs.append(logprob_entry(lp_rows[i * qr + j], s.params.logprobs))
+                emitted.append(row[j])
+                reason = s.append_token(row[j], now)
+                if reason is not None:
+                    self.scheduler.finish(s, reason)
+                    break
+            done.append((s, emitted, reason))
+            self.total_output_tokens += len(emitted)
+        self.scheduler.remove_finished()
+        self.step_count += 1
+        return done
+
     def _complete(self, batch, sampling, handle):
+        if batch.drafts is not None:
+            return self._complete_verify(batch, handle)
         toks = self.runner.fetch(handle)
         # packed logprob rows in sampling order, fetched only when a sequence of the step asked
         lp_rows = self.runner.fetch_logprobs(handle) if len(handle) > 4 and handle[4] is not None else None
@@ -456,7 +578,7 @@ class LLMEngine:
             reason = s.append_token(tok, now)
             if reason is not None:
                 self.scheduler.finish(s, reason)
-            done.append((s, tok, reason))
+            done.append((s, [tok], reason))
         self.scheduler.remove_finished()
         self.step_count += 1
         self.total_output_tokens += len(toks)
@@ -464,10 +586,10 @@ class LLMEngine:
 
     @staticmethod
     def _outputs(done) -> List[RequestOutput]:
-        return [RequestOutput(s.request_id, [tok], reason is not None, reason.value if reason else None,
+        return [RequestOutput(s.request_id, toks, reason is not None, reason.value if reason else None,
                               len(s.prompt_ids), len(s.output_ids), seq_metrics(s) if reason else None,
-                              [s.logprobs[-1]] if s.logprobs is not None else None)
-                for s, tok, reason in done]
+                              s.logprobs[-len(toks):] if s.logprobs is not None else None)
+                for s, toks, reason in done]
 
     def generate(self, prompts: List[List[int]], params: SamplingParams) -> List[List[int]]:
         seqs = [self.add_request(p, dataclasses.replace(params)) for p in prompts]

@@ -54,6 +54,9 @@ class RunnerConfig:
     hip_graphs: bool = True
     graph_batch_sizes: Tuple[int, ...] = ()
     kv_cache_dtype: str = "bf16"     # "bf16" (the model dtype) | "fp8" (OCP e4m3 + per-layer scales)
+    # speculative decoding: query rows per sequence of a verify step (k drafts + 1); 0 = off, and
+    # then nothing below differs from a runner that never heard of it
+    spec_qr: int = 0
 
 
 # Long-context decode merges its partitions in a second kernel (an in-kernel last-arriver merge
@@ -66,16 +69,21 @@ class RunnerConfig:
 class _Layout:
     """Fixed offsets of every per-step int32 section inside one staging buffer."""
 
-    def __init__(self, max_tokens: int, max_seqs: int, max_blocks: int, lora: bool = False):
+    def __init__(self, max_tokens: int, max_seqs: int, max_blocks: int, lora: bool = False, max_samples: int = 0):
         self.max_tokens, self.max_seqs, self.max_blocks = max_tokens, max_seqs, max_blocks
         off = 0
         self.sections = {}
+        # max_samples > 0 (speculative decoding): a verify step samples every row of every sequence,
+        # so the per-sampling-row sections hold that many rows, and "verify_rows" holds the real rows
+        # of each sequence; 0: one sampling row per sequence, today's sizes and offsets
+        ms = max(max_samples, max_seqs)
         # "lora_idx": the adapter slot of every TOKEN row (-1: none); only with adapters configured
         for name, n in (("header", 16), ("input_ids", max_tokens), ("positions", max_tokens), ("slots", max_tokens),
-                        ("context_lens", max_seqs), ("cu_q", max_seqs + 1), ("cu_rel", max_seqs + 1), ("sample_idx", max_seqs),
-                        ("temperature", max_seqs), ("top_k", max_seqs), ("top_p", max_seqs), ("min_p", max_seqs),
-                        ("seeds", max_seqs), ("offsets", max_seqs), ("pen_slot", max_seqs), ("rep", max_seqs),
-                        ("freq", max_seqs), ("pres", max_seqs), ("logprobs", max_seqs),
+                        ("context_lens", max_seqs), ("cu_q", max_seqs + 1), ("cu_rel", max_seqs + 1), ("sample_idx", ms),
+                        ("temperature", ms), ("top_k", ms), ("top_p", ms), ("min_p", ms),
+                        ("seeds", ms), ("offsets", ms), ("pen_slot", ms), ("rep", ms),
+                        ("freq", ms), ("pres", ms), ("logprobs", ms),
+                        *((("verify_rows", max_seqs),) if max_samples else ()),
                         *((("lora_idx", max_tokens),) if lora else ()),
                         ("block_tables", max_seqs * max_blocks)):
             self.sections[name] = (off, n)
@@ -114,7 +122,15 @@ class ModelRunner:
         # resident LoRA adapters (models/lora.py LoraState; the engine enables them on the model
         # before it builds the runner): a per-token slot section and a LoRA variant of every graph
         self.lora = getattr(model, "lora", None)
-        self.layout = _Layout(self.max_step_tokens, cfg.max_num_seqs, self.max_blocks, lora=self.lora is not None)
+        # speculative decoding: a verify step holds spec_qr rows per sequence, at most as many rows
+        # as a decode step may have (the decode chain's row limit, the token budget)
+        self.spec_qr = int(cfg.spec_qr)
+        self.verify_max_seqs = (min(cfg.max_num_seqs, min(gemm.DECODE_MAX_M, self.max_step_tokens) // self.spec_qr)
+                                if self.spec_qr else 0)
+        max_samples = max(cfg.max_num_seqs, self.verify_max_seqs * self.spec_qr) if self.spec_qr else 0
+        self.layout = _Layout(self.max_step_tokens, cfg.max_num_seqs, self.max_blocks, lora=self.lora is not None,
+                              max_samples=max_samples)
+        n_samp = max_samples or cfg.max_num_seqs  # sampling rows of the largest step
         pin = device.type == "cuda"
         # two pinned staging buffers used alternately: a step may be packed while the previous
         # step's H2D copy is still queued behind the GPU (continuation launches, LLMEngine.step)
@@ -129,14 +145,14 @@ class ModelRunner:
         if self.lora is not None:
             self.lora.idx = self.d["lora_idx"]  # the kernels read the staged section itself
         self._step_lora = 0  # the step being packed has a row with an adapter
-        self._tok_hosts = [torch.zeros(cfg.max_num_seqs, dtype=torch.int32, pin_memory=pin) for _ in range(2)]
+        self._tok_hosts = [torch.zeros(n_samp, dtype=torch.int32, pin_memory=pin) for _ in range(2)]
         self._tok_events = [None, None]
         # per-token logprobs (ops/sampler.py logprobs): one packed record per sampling row, written
         # by the kernel right after the sampler (inside every decode graph); rows whose request did
         # not ask (section "logprobs" = -1) cost one early-returning workgroup.  The host copies
         # pair with _tok_hosts and are fetched only for steps in which some sequence asked.
-        self.lp_dev = torch.zeros((cfg.max_num_seqs, sampler_ops.LOGPROB_WORDS), dtype=torch.int32, device=device)
-        self._lp_hosts = [torch.zeros((cfg.max_num_seqs, sampler_ops.LOGPROB_WORDS), dtype=torch.int32,
+        self.lp_dev = torch.zeros((n_samp, sampler_ops.LOGPROB_WORDS), dtype=torch.int32, device=device)
+        self._lp_hosts = [torch.zeros((n_samp, sampler_ops.LOGPROB_WORDS), dtype=torch.int32,
                                       pin_memory=pin) for _ in range(2)]
         self._tok_i = 0
         # sampling penalties / logit_bias (ops/penalties.py): device-resident token history, one
@@ -183,6 +199,15 @@ class ModelRunner:
                                                               kv_heads=a0.nkv)
         self.stats = {"steps": 0, "graph_steps": 0, "short_graph_steps": 0, "tokens": 0, "seed_msgs": 0,
                       "lora_steps": 0, "lora_graph_steps": 0}
+        # verify steps of speculative decoding: graphs per sequence-count bucket (captured only when
+        # configured) and partition slabs for verify_max_seqs x spec_qr rows
+        self.verify_graphs: Dict[int, torch.cuda.CUDAGraph] = {}
+        self.verify_graph_out: Dict[int, torch.Tensor] = {}
+        self.vpart_o = self.vpart_ml = None
+        if self.spec_qr:
+            self.vpart_o, self.vpart_ml = attn_ops.verify_workspace(self.verify_max_seqs, self.spec_qr, a0.nq,
+                                                                    self.max_blocks, self.bs, device, kv_heads=a0.nkv)
+            self.stats.update(verify_steps=0, verify_graph_steps=0)
         self.keep_logits = False  # tests: keep the last eager step's logits
         self.last_logits = None
         # diagnostics (tools/tp_rehearsal.py): every step's logits, graphed steps included (a copy
@@ -310,6 +335,108 @@ class ModelRunner:
                 h["logprobs"][r] = p.logprobs
                 want_lp = True
         return T, n, want_lp
+
+    def _pack_verify(self, batch: ScheduledBatch):
+        """A verify step (speculative decoding): sequence i owns the ``qr`` rows ``i * qr + j``.  Rows
+        ``j < R = 1 + len(drafts)`` carry [last token, drafts...] at positions ``num_computed + j`` with
+        their KV slots; the rest are padding (token 0, position 0, slot -1).  Every row samples, with
+        its sequence's parameters and ``offset = len(output_ids) + j``; penalty, grammar and logprob
+        fields sit on row 0 of a sequence without drafts (the only ones that have them) or are neutral.
+        -> (T, n, want_lp)"""
+        seqs, drafts, qr = batch.decodes, batch.drafts, self.spec_qr
+        n = len(seqs)
+        T = n * qr
+        sids = np.fromiter((s.seq_id for s in seqs), dtype=np.int64, count=n)
+        ncomp = np.fromiter((s.num_computed for s in seqs), dtype=np.int32, count=n)
+        nnew = np.fromiter((1 + len(d) for d in drafts), dtype=np.int32, count=n)
+        toks: List[int] = []
+        for s, d in zip(seqs, drafts):
+            toks.append(s.output_ids[-1] if s.output_ids else s.prompt_ids[-1])
+            toks.extend(d)
+        R_all = len(toks)
+        ids, pos, slot = (np.empty(R_all, dtype=np.int32) for _ in range(3))
+        h = self.h
+        self.bm.pack_step(sids, ncomp, nnew, np.asarray(toks, dtype=np.int32), ids, pos, slot, h["block_tables"],
+                          self.max_blocks, h["context_lens"], h["cu_q"])
+        cu = h["cu_q"][:n + 1].astype(np.int64)
+        dest = np.repeat(np.arange(n, dtype=np.int64) * qr - cu[:-1], nnew) + np.arange(R_all, dtype=np.int64)
+        h["input_ids"][:T] = 0
+        h["positions"][:T] = 0
+        h["slots"][:T] = -1
+        h["input_ids"][dest] = ids
+        h["positions"][dest] = pos
+        h["slots"][dest] = slot
+        h["verify_rows"][:n] = nnew
+        h["sample_idx"][:T] = np.arange(T, dtype=np.int32)
+        h["logprobs"][:T] = -1
+        self._neutral_penalties(T)
+        # per-sequence sampling parameters, repeated over the sequence's qr rows
+        ps = [s.params for s in seqs]
+        for name, dt, vals in (("temperature", np.float32, [p.temperature for p in ps]),
+                               ("top_k", np.int32, [p.top_k for p in ps]), ("top_p", np.float32, [p.top_p for p in ps]),
+                               ("min_p", np.float32, [p.min_p for p in ps]), ("seeds", np.int32, [s.seed for s in seqs])):
+            h[name][:T] = np.repeat(np.asarray(vals, dtype=dt), qr)
+        h["offsets"][:T] = (np.repeat(np.fromiter((len(s.output_ids) for s in seqs), dtype=np.int32, count=n), qr)
+                            + np.tile(np.arange(qr, dtype=np.int32), n))
+        pen = self._pen_slot
+        want_lp = False
+        for i, s in enumerate(seqs):
+            if pen and s.seq_id in pen:  # (no drafts: one real row)
+                self._fill_penalties(i * qr, s)
+            if ps[i].logprobs is not None:
+                h["logprobs"][i * qr:i * qr + int(nnew[i])] = ps[i].logprobs
+                want_lp = True
+        return T, n, want_lp
+
+    def _pad_verify(self, n: int, g: int) -> None:
+        """Sequences n..g of a verify graph bucket: no context, every row padding."""
+        if g <= n:
+            return
+        h, qr = self.h, self.spec_qr
+        a, b = n * qr, g * qr
+        h["input_ids"][a:b] = 0
+        h["positions"][a:b] = 0
+        h["slots"][a:b] = -1
+        h["context_lens"][n:g] = 0
+        h["verify_rows"][n:g] = 1
+        h["sample_idx"][a:b] = np.arange(a, b, dtype=np.int32)
+        h["temperature"][a:b] = 0.0
+        h["top_k"][a:b] = 0
+        h["top_p"][a:b] = 1.0
+        h["min_p"][a:b] = 0.0
+        h["logprobs"][a:b] = -1
+        h["pen_slot"][a:b] = -1
+
+    def _verify_metadata(self, n: int) -> attn_ops.AttnMetadata:
+        """Outside attention a verify step is a decode step of n * qr rows; its attention reads the
+        per-sequence block tables, contexts and real-row counts, at the block-table capacity bound
+        (eager and replayed steps take the same partition plan)."""
+        d, qr = self.d, self.spec_qr
+        T = n * qr
+        return attn_ops.AttnMetadata(
+            num_decode=T, num_prefill=0, num_prefill_tokens=0, max_prefill_q_len=0, slot_mapping=d["slots"][:T],
+            decode_part_o=self.vpart_o, decode_part_ml=self.vpart_ml, decode_max_ctx=0, verify_qr=qr,
+            verify_rows=d["verify_rows"][:n], verify_block_tables=d["block_tables"][:n],
+            verify_context_lens=d["context_lens"][:n])
+
+    def launch_verify(self, batch: ScheduledBatch):
+        """:meth:`launch` of a pure-decode batch whose sequences carry drafts (``batch.drafts``): one
+        verify step, replayed from the verify graph of the sequence-count bucket when captured."""
+        self._seed_penalties(batch.decodes)
+        self._next_staging()
+        T, n, want_lp = self._pack_verify(batch)
+        g = 0
+        if self.verify_graphs and self.allow_graphs:
+            g = next((b for b in sorted(self.verify_graphs) if b >= n), 0)
+            self._pad_verify(n, g)
+        qr = self.spec_qr
+        h = self.h
+        if self.lora is not None:  # (the engine refuses the combination; rows stay base rows)
+            h["lora_idx"][:max(n, g) * qr] = -1
+        h["header"][:11] = (self.MODE_RUN, T, n, T, T, 0, g, 0, 0, 0, qr)
+        self._publish(max(n, g))
+        toks = self._run(T, n, T, T, 0, g, 0, 0, qr)
+        return self._handle(toks, T, want_lp)
 
     # ------------------------------------------------------------------ LoRA
     def _fill_lora(self, seqs: List[Sequence], T: int) -> None:
@@ -569,6 +696,8 @@ class ModelRunner:
     def launch(self, batch: ScheduledBatch):
         """Enqueue one step (pack → H2D → graph replay / eager forward → sample → async D2H of
         the sampled ids) without waiting for the GPU; :meth:`fetch` returns the ids."""
+        if batch.drafts is not None:
+            return self.launch_verify(batch)
         sampling = batch.sampling_seqs()
         self._seed_penalties(sampling)
         self._next_staging()
@@ -593,7 +722,7 @@ class ModelRunner:
                 self._pad_decode(nd, g)
         short = self._short(g, nd)
         lora = self._step_lora if self.lora is not None else 0
-        h["header"][:10] = (self.MODE_RUN, T, n, nd, ns, max_q, g, short, 0, lora)
+        h["header"][:11] = (self.MODE_RUN, T, n, nd, ns, max_q, g, short, 0, lora, 0)
         self._publish(max(n, g))
         toks = self._run(T, n, nd, ns, max_q, g, short, lora)
         return self._handle(toks, ns, want_lp)
@@ -702,7 +831,7 @@ class ModelRunner:
             lora = self._step_lora
         self._pad_decode(n, g)
         short = self._short(g, n)
-        h["header"][:10] = (self.MODE_RUN, T, n, n, n, 0, g, short, 1, lora)
+        h["header"][:11] = (self.MODE_RUN, T, n, n, n, 0, g, short, 1, lora, 0)
         self._publish(max(n, g))
         self.d["input_ids"][:n].copy_(prev[3][:n])  # step k's sampled ids, stream-ordered
         return self._handle(self._run(T, n, n, n, 0, g, short, lora), n, want_lp)
@@ -784,7 +913,7 @@ class ModelRunner:
                 return
             if nbytes == -3:  # the leader's process is gone (SIGKILL, OOM, crash): end this rank
                 raise TPPeerError("TP leader process died; this worker exits for its supervisor to restart the group")
-            mode, T, n, nd, ns, max_q, g, short, cont, lora = (int(v) for v in self.h["header"][:10])
+            mode, T, n, nd, ns, max_q, g, short, cont, lora, qr = (int(v) for v in self.h["header"][:11])
             if mode == self.MODE_STOP:
                 return
             if mode == self.MODE_SEED:
@@ -803,7 +932,7 @@ class ModelRunner:
             with torch.inference_mode():
                 if cont:
                     self.d["input_ids"][:n].copy_(self._prev_toks[:n])
-                toks = self._run(T, n, nd, ns, max_q, g, short, lora)
+                toks = self._run(T, n, nd, ns, max_q, g, short, lora, qr)
             if toks is not None:
                 self._prev_toks = toks
             self.stats["steps"] += 1
@@ -831,7 +960,8 @@ class ModelRunner:
             self.graph_out.clear()
             self.short_graphs.clear()
             self.short_graph_out.clear()
-            for d in (self.lora_graphs, self.lora_graph_out, self.lora_short_graphs, self.lora_short_graph_out):
+            for d in (self.lora_graphs, self.lora_graph_out, self.lora_short_graphs, self.lora_short_graph_out,
+                      self.verify_graphs, self.verify_graph_out):
                 d.clear()
             self._graph_logits.clear()
             self.graph_pool = None
@@ -861,8 +991,21 @@ class ModelRunner:
             self.channel.publish(self._hnp[self._cur], 64, 60000)
             self.channel.close()
 
-    def _run(self, T: int, n: int, nd: int, ns: int, max_q: int, g: int, short: int = 0, lora: int = 0):
+    def _run(self, T: int, n: int, nd: int, ns: int, max_q: int, g: int, short: int = 0, lora: int = 0, qr: int = 0):
         d = self.d
+        if qr:  # a verify step: n sequences x qr rows, every row sampled
+            self.stats["verify_steps"] += 1
+            if g:
+                self.verify_graphs[g].replay()
+                self.stats["verify_graph_steps"] += 1
+                if self.debug_logits:
+                    self.last_logits = self._graph_logits[(g, "verify")]
+                return self.verify_graph_out[g]
+            hidden = self.model(d["input_ids"][:T], d["positions"][:T], self._verify_metadata(n), self.kv_caches)
+            logits = self.model.compute_logits(hidden)
+            if self.keep_logits or self.debug_logits:
+                self.last_logits = logits
+            return self._sample(logits, T)
         if self.lora is not None:
             self.lora.active = bool(lora)  # the model's LoRA form for this step (eager; graphs hold theirs)
             self.stats["lora_steps"] += int(bool(lora))
@@ -958,7 +1101,9 @@ class ModelRunner:
         self.h["pen_slot"][:] = -1
         if self.lora is not None:
             self.h["lora_idx"][:] = -1
-        self.h["sample_idx"][: self.cfg.max_num_seqs] = np.arange(self.cfg.max_num_seqs, dtype=np.int32)
+        self.h["sample_idx"][:] = np.arange(self.h["sample_idx"].shape[0], dtype=np.int32)
+        if self.spec_qr:
+            self.h["verify_rows"][:] = 1
         self.dev_buf.copy_(self.host_buf)
         torch.cuda.synchronize(self.device)
         stream = torch.cuda.Stream(self.device)
@@ -997,4 +1142,37 @@ class ModelRunner:
                 (self.short_graph_out if short else self.graph_out)[g] = out
         if self.lora is not None:
             self.lora.active = False
+        if self.spec_qr:
+            self._capture_verify_graphs(sizes, stream)
         torch.cuda.synchronize(self.device)
+
+    def verify_graph_sizes(self, sizes: Optional[List[int]] = None) -> List[int]:
+        """The decode buckets a verify graph exists for: those whose rows fit a verify step."""
+        return [g for g in (sizes or self.default_graph_sizes()) if g <= self.verify_max_seqs]
+
+    def _capture_verify_graphs(self, sizes: List[int], stream) -> None:
+        """One verify graph per decode bucket g with g * qr rows within the decode row limit, on the
+        dummy state of capture_graphs (context 1, one real row per sequence, no cache writes)."""
+        d, qr = self.d, self.spec_qr
+        for g in sorted(self.verify_graph_sizes(sizes), reverse=True):
+            T = g * qr
+            md = self._verify_metadata(g)
+
+            def run():
+                hidden = self.model(d["input_ids"][:T], d["positions"][:T], md, self.kv_caches)
+                logits = self.model.compute_logits(hidden)
+                if self.debug_logits:
+                    self._graph_logits[(g, "verify")] = logits.clone()
+                return self._sample(logits, T)
+
+            stream.wait_stream(torch.cuda.current_stream(self.device))
+            with torch.cuda.stream(stream):
+                run()
+            torch.cuda.current_stream(self.device).wait_stream(stream)
+            graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graph, pool=self.graph_pool):
+                out = run()
+            if self.graph_pool is None:
+                self.graph_pool = graph.pool()
+            self.verify_graphs[g] = graph
+            self.verify_graph_out[g] = out

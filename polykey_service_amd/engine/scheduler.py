@@ -43,6 +43,9 @@ class ScheduledBatch:
     decodes: List[Sequence]
     prefills: List[Tuple[Sequence, int]]   # (seq, chunk length)
     preempted: List[Sequence]
+    # speculative decoding (LLMEngine._propose): the draft tokens of every decode sequence, in order
+    # -- the batch then runs as one verify step; None: an ordinary step
+    drafts: Optional[List[List[int]]] = None
 
     @property
     def num_tokens(self) -> int:

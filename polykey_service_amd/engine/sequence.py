@@ -60,6 +60,9 @@ class SamplingParams:
     guided_suffix: str = ""       # literal text after the guided_json value (a forced tool call's closing)
     # the LoRA adapter the request runs on (a name from EngineConfig.lora_modules); None = the base model
     lora: Optional[str] = None
+    # speculative decoding (engine/spec.py): None = the engine's setting, False = never draft for this
+    # request; True on an engine without speculation is ignored
+    speculative: Optional[bool] = None
 
     @property
     def has_penalties(self) -> bool:
@@ -115,6 +118,8 @@ class SamplingParams:
             raise ValueError("guided_json must be a JSON Schema (a dict, or its JSON text)")
         if self.lora is not None and (not isinstance(self.lora, str) or not self.lora):
             raise ValueError("lora must be the name of a served adapter")
+        if self.speculative is not None and not isinstance(self.speculative, bool):
+            raise ValueError("speculative must be a boolean")
         if not isinstance(self.guided_suffix, str) or (self.guided_suffix and self.guided_json is None):
             raise ValueError("guided_suffix needs guided_json")
         if (self.guided_regex is not None) + bool(gc) + (self.guided_json is not None) > 1:
@@ -176,6 +181,9 @@ class SamplingParams:
                 elif f.name == "lora":
                     if not isinstance(v, str) or not v:
                         raise ValueError("lora must be the name of a served adapter")
+                elif f.name == "speculative":
+                    if not isinstance(v, bool):
+                        raise ValueError("speculative must be a boolean")
                 elif f.name == "logprobs":
                     if isinstance(v, bool) or (isinstance(v, float) and v != int(v)):
                         raise ValueError(f"logprobs must be an integer in [0, {MAX_LOGPROBS}]")
@@ -204,7 +212,7 @@ class Sequence:
     __slots__ = ("seq_id", "request_id", "prompt_ids", "output_ids", "params", "status", "num_computed",
                  "arrival", "first_scheduled", "first_token_time", "finish_time", "finish_reason",
                  "num_preemptions", "eos_token_id", "token_times", "user", "num_cached_tokens",
-                 "cache_salt", "logprobs", "grammar")
+                 "cache_salt", "logprobs", "grammar", "spec_state", "spec_drafted", "spec_accepted")
 
     def __init__(self, request_id: str, prompt_ids: List[int], params: SamplingParams, eos_token_id: int = -1,
                  user=None, cache_salt: Optional[str] = None):
@@ -227,6 +235,11 @@ class Sequence:
         # one (logprob, [(id, logprob) x n]) per output token; None unless params.logprobs is set
         self.logprobs: Optional[list] = [] if getattr(params, "logprobs", None) is not None else None
         self.grammar = None  # the request's compiled constraint (engine/grammar.py), set by add_request
+        # speculative decoding: the proposer's per-sequence state, and draft tokens proposed / accepted
+        # (None on an engine without speculation: seq_metrics then reports neither)
+        self.spec_state = None
+        self.spec_drafted: Optional[int] = None
+        self.spec_accepted: Optional[int] = None
         self.user = user
         # prefix-cache namespace (Scheduler._salt); None = the request's params.cache_salt
         self.cache_salt = cache_salt if cache_salt is not None else getattr(params, "cache_salt", None)
@@ -288,8 +301,12 @@ def seq_metrics(s: Sequence) -> dict:
     itl = None
     if len(s.token_times) > 1:
         itl = (s.token_times[-1] - s.token_times[0]) / (len(s.token_times) - 1)
-    return {
+    m = {
         "queue_s": (s.first_scheduled - t0) if s.first_scheduled else None,
         "ttft_s": ttft, "e2e_s": e2e, "mean_itl_s": itl, "preemptions": s.num_preemptions,
         "cached_prompt_tokens": s.num_cached_tokens,
     }
+    if s.spec_drafted is not None:  # an engine with speculative decoding configured
+        m["spec_drafted"] = s.spec_drafted
+        m["spec_accepted"] = s.spec_accepted
+    return m

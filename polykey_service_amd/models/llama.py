@@ -224,8 +224,13 @@ class LlamaAttention(nn.Module):
         """RoPE + KV-cache write + paged attention from the QKV projection's split-K slabs (after any
         LoRA delta) -> [T, nq * hd].  Pure decode: the attention kernel does all of it in one launch.
         Steps with prefill, and every step of a QK-norm model (whose norm only the slab writer
-        applies): the slab writer, then q-only paged attention."""
+        applies): the slab writer, then q-only paged attention.  A verify step of speculative decoding
+        (``md.verify_qr`` rows per sequence): the slab writer, then the verify attention."""
         k_cache, v_cache = kv
+        if md.verify_qr > 0:
+            q = gemm.qkv_reduce_rope_cache(p, positions, cos_sin, k_cache, v_cache, md.slot_mapping, self.nq, self.nkv,
+                                           q_norm=self.q_norm, k_norm=self.k_norm, eps=self.qk_eps)
+            return attn_ops.paged_verify(q, k_cache, v_cache, md, self.scale)
         if self.q_norm is None and md.num_prefill == 0:
             return attn_ops.paged_decode_from_qkv(p, positions, cos_sin, k_cache, v_cache, md, self.scale,
                                                   self.nq, self.nkv, k_scale=self.k_scale, v_scale=self.v_scale)
@@ -281,6 +286,8 @@ class LlamaAttention(nn.Module):
                                 self.hd, k_scale=self.k_scale, v_scale=self.v_scale, q_norm=self.q_norm,
                                 k_norm=self.k_norm, eps=self.qk_eps)
         q = qkv.view(qkv.shape[0], self.nq + 2 * self.nkv, self.hd)[:, :self.nq]
+        if md.verify_qr > 0:  # a verify step of speculative decoding (bf16 cache)
+            return attn_ops.paged_verify(q, k_cache, v_cache, md, self.scale)
         return attn_ops.paged_attention(q, k_cache, v_cache, md, self.scale, k_scale=self.k_scale,
                                         v_scale=self.v_scale)
 
@@ -752,6 +759,8 @@ class LlamaForCausalLM(nn.Module):
         if self.wq is not None:  # quantised weights: the two-launch forms only (the fused launches are bf16-only)
             return False
         if at.q_norm is not None:  # QK-norm: the fused launch has no norm between the slab sum and RoPE
+            return False
+        if md.verify_qr > 0:  # a verify step: the slab writer, then the verify attention (attend_slabs)
             return False
         return (md.num_prefill == 0 and gemm.QKV_ATTN_FUSED and at.nkv >= gemm.QKV_ATTN_MIN_KV
                 and gemm.fused_rows_ok(T, nparts) and md.num_decode == T

@@ -33,6 +33,12 @@ class AttnMetadata:
     decode_part_o: Optional[torch.Tensor] = None         # split-K workspace
     decode_part_ml: Optional[torch.Tensor] = None
     decode_max_ctx: int = 0  # bound on every decode context of the step (0: block-table capacity)
+    # A verify step of speculative decoding (:func:`paged_verify`): ``verify_qr`` > 0 query rows per
+    # sequence, ``num_decode`` = n_seqs * verify_qr rows in all, sequence s owning rows s * qr + j
+    verify_qr: int = 0
+    verify_rows: Optional[torch.Tensor] = None           # [n_seqs] int32: real rows R of each sequence, 1..qr
+    verify_block_tables: Optional[torch.Tensor] = None   # [n_seqs, MB] int32
+    verify_context_lens: Optional[torch.Tensor] = None   # [n_seqs] int32: keys cached, the R new ones included
 
     @property
     def num_tokens(self) -> int:
@@ -185,6 +191,66 @@ def paged_attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tenso
                     bt.data_ptr(), md.prefill_context_lens.data_ptr(), md.prefill_cu_q.data_ptr(),
                     md.num_prefill, nq, nkv, bs, bt.shape[1], q.stride(0), out.stride(0), int(md.max_prefill_q_len),
                     float(scale), *kv, stream)
+    return out
+
+
+def verify_workspace(n_seqs: int, qr: int, n_q: int, max_blocks: int, block_size: int, device, n_kv: int = 0,
+                     kv_heads: Optional[int] = None) -> tuple:
+    """Partition slabs of :func:`paged_verify`: the launch plan is the decode plan of ``n_seqs``
+    sequences and every slab row holds one of the ``n_seqs * qr`` query rows, i.e. the decode
+    workspace of ``n_seqs`` sequences with ``qr * n_q`` heads."""
+    return decode_workspace(n_seqs, n_q * qr, max_blocks, block_size, device, n_kv, kv_heads)
+
+
+def paged_verify(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, md: AttnMetadata, scale: float,
+                 out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Attention of a verify step (speculative decoding).  q: [n_seqs * qr, nq, 128] view, sequence s
+    owning rows ``s * qr + j``; the first ``R = md.verify_rows[s]`` (1..qr) are real, and
+    ``C = md.verify_context_lens[s]`` counts the keys in the cache *including* the R written this
+    step.  Row ``j < R`` attends keys ``0 .. C - R + j``; rows ``j >= R`` and every row of a sequence
+    with ``C <= 0`` come out as exact zeros.  Returns out [n_seqs * qr, nq * 128] (contiguous rows).
+
+    bf16 caches only, ``qr * (nq / nkv) <= 16`` (the columns of one MFMA tile): anything else is an
+    error.  ``md.decode_part_o`` / ``decode_part_ml`` are sized by :func:`verify_workspace`.  R is
+    checked here when ``md.verify_rows`` lives on the host; on the GPU the packer guarantees it (the
+    kernel reads rows past qr as qr and R <= 0 as a sequence of padding rows)."""
+    T, nq, hd = q.shape
+    qr = int(md.verify_qr)
+    nkv, bs = k_cache.shape[1], k_cache.shape[2]
+    if qr < 1 or T % qr or nq % nkv or qr * (nq // nkv) > 16:
+        raise ValueError(f"paged_verify: {T} rows of {qr} per sequence, GQA group {nq // max(nkv, 1)}: "
+                         f"needs qr >= 1, whole sequences and qr * group <= 16")
+    if k_cache.dtype == FP8 or v_cache.dtype == FP8 or (q.is_cuda and cache_is_fp8(k_cache, v_cache)):
+        raise TypeError("paged_verify reads a bfloat16 KV cache only (an FP8 cache has no verify kernel)")
+    n_seqs = T // qr
+    rows, ctxs, bt = md.verify_rows, md.verify_context_lens, md.verify_block_tables
+    assert rows.shape[0] == n_seqs and ctxs.shape[0] == n_seqs and bt.shape[0] == n_seqs
+    if out is None:
+        out = torch.empty((T, nq * hd), dtype=q.dtype, device=q.device)
+    if not q.is_cuda:
+        R, C = rows.tolist(), ctxs.tolist()
+        if any(not 1 <= r <= qr for r in R):
+            raise ValueError(f"paged_verify: verify_rows outside 1..{qr}: {R}")
+        out.zero_()
+        live = [s for s in range(n_seqs) if C[s] > 0]
+        if live:  # the real rows of every live sequence, as R-token chunks ending at key C - 1
+            idx = torch.tensor([s * qr + j for s in live for j in range(R[s])], dtype=torch.long)
+            cu = torch.tensor([0] + [R[s] for s in live], dtype=torch.int32).cumsum(0).to(torch.int32)
+            sel = torch.tensor(live, dtype=torch.long)
+            md_r = AttnMetadata(num_decode=0, num_prefill=len(live), num_prefill_tokens=idx.numel(),
+                                max_prefill_q_len=max(R[s] for s in live), slot_mapping=md.slot_mapping,
+                                prefill_block_tables=bt[sel], prefill_context_lens=ctxs[sel], prefill_cu_q=cu)
+            o = torch.empty((idx.numel(), nq * hd), dtype=q.dtype)
+            _reference(q[idx].contiguous(), k_cache, v_cache, md_r, scale, o)
+            out[idx] = o
+        return out
+    assert hd == 128 and q.stride(-1) == 1 and q.stride(1) == hd and out.stride(0) == nq * hd
+    assert rows.dtype == torch.int32 and ctxs.dtype == torch.int32 and bt.dtype == torch.int32
+    apply_decode_fill()
+    native.call("pk_paged_verify", out.data_ptr(), q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(),
+                bt.data_ptr(), ctxs.data_ptr(), rows.data_ptr(), native.ptr(md.decode_part_o) or 0,
+                native.ptr(md.decode_part_ml) or 0, n_seqs, qr, nq, nkv, bs, bt.stride(0), q.stride(0), out.stride(0),
+                float(scale), int(md.decode_max_ctx), 0, native.stream_ptr())
     return out
 
 

@@ -41,6 +41,8 @@ SIGNATURES = {
     # QK-norm (Qwen3): q_norm_w, k_norm_w, eps after the slot mapping
     "pk_rope_and_cache_qknorm": [P, P, P, P, P, P, P, P, F32, I32, I32, I32, I32, I32, I32, *KV, P],
     "pk_paged_decode": [P, P, P, P, P, P, P, P, I32, I32, I32, I32, I32, I32, I32, F32, I32, *KV, P],
+    # verify step of speculative decoding: n_rows after the context lengths, qr after n_seqs; bf16 caches only
+    "pk_paged_verify": [P, P, P, P, P, P, P, P, P, I32, I32, I32, I32, I32, I32, I32, I32, F32, I32, I32, P],
     "pk_set_decode_z": [I32],
     "pk_set_decode_fill": [I32],
     "pk_paged_decode_qkv": [P, P, I32, I32, P, P, P, P, P, P, P, P, P, I32, I32, I32, I32, I32, I32, F32, I32, *KV, P],

@@ -342,6 +342,68 @@ def paged_attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tenso
     return out
 
 
+VERIFY_MUTANTS = ("limit+1", "limit-1", "ignore_rows", "head_major", "ctx_excludes_new")
+
+
+def verify_limits(context_lens, n_rows, qr: int, nq: int, G: int, mutant: Optional[str] = None) -> torch.Tensor:
+    """[n_seqs * qr, nq] int64: the last key row ``s * qr + j`` of head ``hq`` attends in a verify
+    step, -1 for a row that attends nothing (a padding row ``j >= R``, a sequence with ``C <= 0``).
+    The contract: ``C - R + j`` for ``j < R``.
+
+    ``mutant`` (tests) is a deliberate defect: ``"limit+1"`` / ``"limit-1"`` (off by one),
+    ``"ignore_rows"`` (R taken as qr: padding rows attend, real rows shift), ``"head_major"`` (the row
+    of tile column c = j * G + head taken as c % qr, as if the columns were ordered head-major),
+    ``"ctx_excludes_new"`` (C taken as the keys *before* this step's: limit C + j)."""
+    assert mutant is None or mutant in VERIFY_MUTANTS, mutant
+    lim = torch.full((len(context_lens) * qr, nq), -1, dtype=torch.int64)
+    for s, (C, R) in enumerate(zip((int(c) for c in context_lens), (int(r) for r in n_rows))):
+        if C <= 0:
+            continue
+        Rm = qr if mutant == "ignore_rows" else min(R, qr)
+        for j in range(Rm):
+            for hq in range(nq):
+                jl = (j * G + hq % G) % qr if mutant == "head_major" else j
+                if jl >= Rm:
+                    continue
+                l = C - Rm + jl
+                l += {"limit+1": 1, "limit-1": -1, "ctx_excludes_new": Rm}.get(mutant, 0)
+                lim[s * qr + j, hq] = max(l, -1)
+    return lim
+
+
+def paged_verify(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, block_tables: torch.Tensor,
+                 context_lens, n_rows, qr: int, scale: float, dtype=torch.float32, mutant: Optional[str] = None):
+    """Attention of a verify step (speculative decoding), sums in ``dtype`` (float64: the tests'
+    reference).  q: [n_seqs * qr, nq, D]; sequence s owns rows ``s * qr + j``, the first
+    ``R = n_rows[s]`` of them real; ``C = context_lens[s]`` counts the cached keys including the R
+    written this step.  Every (row, head) attends keys ``0 .. verify_limits(...)``; a limit of -1
+    gives zeros.  -> (out, A) both [n_seqs * qr, nq, D] in ``dtype``, ``A = sum_j p_j |v_j|`` (what a
+    rounding bound is measured against).  A mutant's limit may reach past C (never past the block
+    table's capacity): it then reads whatever the cache holds there."""
+    T, nq, D = q.shape
+    nkv = k_cache.shape[1]
+    G = nq // nkv
+    lim = verify_limits(context_lens, n_rows, qr, nq, G, mutant)
+    out = torch.zeros((T, nq, D), dtype=dtype)
+    A = torch.zeros((T, nq, D), dtype=dtype)
+    cap = block_tables.shape[1] * k_cache.shape[2]
+    for s in range(len(context_lens)):
+        n = min(int(lim[s * qr:(s + 1) * qr].max()) + 1, cap)
+        if n <= 0:
+            continue
+        k, v = gather_kv(k_cache, v_cache, block_tables[s], n)
+        k, v = k.to(dtype), v.to(dtype)
+        for j in range(qr):
+            for hq in range(nq):
+                m = min(int(lim[s * qr + j, hq]) + 1, n)
+                if m <= 0:
+                    continue
+                p = torch.softmax((k[:m, hq // G] @ q[s * qr + j, hq].to(dtype)) * scale, dim=0)
+                out[s * qr + j, hq] = p @ v[:m, hq // G]
+                A[s * qr + j, hq] = p @ v[:m, hq // G].abs()
+    return out, A
+
+
 # --------------------------------------------------------------------------- sampling
 _M32 = np.uint64(0xFFFFFFFF)
 

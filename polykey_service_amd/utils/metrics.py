@@ -52,6 +52,13 @@ class Metrics:
                                    registry=r)
         self.prefix_collisions = Counter("polykey_engine_prefix_cache_rejected", "hash matches rejected by the "
                                          "token / parent check", registry=r)
+        # speculative decoding (engine/spec.py): verify steps, draft tokens fed to them, drafts accepted
+        self.spec_steps = Counter("polykey_engine_spec_steps_total", "verify steps of speculative decoding",
+                                  registry=r)
+        self.spec_drafts = Counter("polykey_engine_spec_draft_tokens_total", "draft tokens fed to verify steps",
+                                   registry=r)
+        self.spec_accepted = Counter("polykey_engine_spec_accepted_tokens_total", "draft tokens accepted by verify "
+                                     "steps", registry=r)
         self._last: dict = {}
         self.cached_blocks = Gauge("polykey_engine_prefix_cache_blocks", "KV blocks registered in the prefix cache",
                                    registry=r)
@@ -92,6 +99,9 @@ class Metrics:
         self._advance(self.prefix_hits, "hits", getattr(bm, "prefix_hits", 0))
         self._advance(self.prefix_collisions, "collisions", getattr(bm, "prefix_collisions", 0))
         self.cached_blocks.set(getattr(bm, "num_cached", 0))
+        self._advance(self.spec_steps, "spec_steps", getattr(engine, "spec_steps", 0))
+        self._advance(self.spec_drafts, "spec_drafts", getattr(engine, "spec_draft_tokens", 0))
+        self._advance(self.spec_accepted, "spec_accepted", getattr(engine, "spec_accepted_tokens", 0))
         n = 0
         for o in outputs:
             n += len(o.new_token_ids)
