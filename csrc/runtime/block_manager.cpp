@@ -35,6 +35,15 @@ class BlockManager : public pk::BlockManagerCore {
     commit_prefix(seq, hashes.data(), tokens.data(), tokens.shape(0), std::min<int64_t>(n, hashes.shape(0)));
   }
 
+  // -> the (src block, dst block) copy pairs (none or one), or None when the fork failed (no state changed)
+  py::object fork_py(int64_t src, int64_t dst, int64_t n_tokens) {
+    std::vector<int32_t> p;
+    if (!fork(src, dst, n_tokens, &p)) return py::none();
+    py::list out;
+    for (size_t i = 0; i + 1 < p.size(); i += 2) out.append(py::make_tuple(p[i], p[i + 1]));
+    return out;
+  }
+
   int64_t pack_step(I64 seq_ids, I32 num_computed, I32 num_new, I32 tokens, I32 input_ids, I32 positions,
                     I32 slot_mapping, I32 block_tables, int max_blocks, I32 context_lens, I32 cu_q) {
     const int64_t n = seq_ids.shape(0);
@@ -84,6 +93,7 @@ PYBIND11_MODULE(_pk_runtime, m) {
       .def("can_allocate", &BlockManager::can_allocate, py::arg("seq"), py::arg("total_tokens"),
            py::arg("admission") = false)
       .def("allocate", &BlockManager::allocate)
+      .def("fork", &BlockManager::fork_py, py::arg("src_seq"), py::arg("dst_seq"), py::arg("n_tokens"))
       .def("free_seq", &BlockManager::free_seq)
       .def("has", &BlockManager::has)
       .def("table", &BlockManager::table)

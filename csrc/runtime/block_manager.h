@@ -86,6 +86,40 @@ class BlockManagerCore {
     tables_.erase(it);
   }
 
+  // Token-granular fork (parallel sampling): `dst`, a sequence without blocks, gets the KV of the
+  // first n_tokens tokens of `src` -- the n_tokens / block_size full blocks by reference (shared
+  // read-only: the caller never writes a position < n_tokens of `dst`) and, for a remainder, one
+  // fresh block whose content the caller copies from src's block of the same index: `pairs` receives
+  // that (src block, dst block), or stays empty.  False, with NO state changed, when `dst` already
+  // has a table, `src` is missing or holds fewer than n_tokens tokens' blocks, n_tokens <= 0, or the
+  // remainder's block cannot be had.
+  bool fork(int64_t src, int64_t dst, int64_t n_tokens, std::vector<int32_t>* pairs) {
+    pairs->clear();
+    auto it = tables_.find(src);
+    if (n_tokens <= 0 || src == dst || tables_.count(dst) || it == tables_.end() ||
+        static_cast<int64_t>(it->second.size()) < blocks_for(n_tokens))
+      return false;
+    const int64_t full = n_tokens / block_size_;
+    const bool rem = n_tokens % block_size_ != 0;
+    if (rem && num_free() < 1) return false;
+    std::vector<int32_t> t(it->second.begin(), it->second.begin() + full);  // (before tables_ may rehash)
+    for (int32_t b : t) {
+      if (in_lru_[b]) {
+        lru_.erase(lru_pos_[b]);
+        in_lru_[b] = 0;
+      }
+      ++ref_[b];
+    }
+    if (rem) {
+      const int32_t from = it->second[full];
+      t.push_back(take_block());
+      pairs->push_back(from);
+      pairs->push_back(t.back());
+    }
+    tables_[dst] = std::move(t);
+    return true;
+  }
+
   // Keyed chained hashes of the full blocks of tokens[0:n] (at most max_out): h_i covers every
   // token of blocks 0..i and the salt.  Never 0.  Lookups verify tokens (match_prefix), so the
   // hash only has to spread, not to be collision-free.

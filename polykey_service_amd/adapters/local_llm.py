@@ -27,6 +27,11 @@ with function tools.  A value out of range is ``INVALID_ARGUMENT``.
 ``guided_regex`` (string), ``guided_choice`` (list of strings) and ``guided_json`` (a JSON Schema
 as a Struct, or as JSON text, which keeps integers exact) constrain the completion
 (engine/grammar.py); an unsupported pattern or schema keyword is ``INVALID_ARGUMENT``.
+``n`` (1..16 and at most the engine's ``max_num_seqs``: parallel sampling) needs ``return: "struct"``;
+the summary then gains ``choices: [{index, text, finish_reason, token_ids?, logprobs?}]`` while the
+top-level ``text`` / ``finish_reason`` stay those of index 0, ``usage.prompt_tokens`` counts the prompt
+once and ``completion_tokens`` sums the choices.  ``n > 1`` with function tools, without the struct, or
+on ``ExecuteToolStream`` is ``INVALID_ARGUMENT``.
 """
 from __future__ import annotations
 
@@ -34,7 +39,7 @@ import time
 from typing import Dict, List, Optional
 
 from .. import proto
-from ..engine.sequence import SamplingParams
+from ..engine.sequence import SamplingParams, check_n
 from ..engine.tokenizer import IncrementalDetokenizer
 from ..service import logprob_format as lpf
 from ..service.base import RequestContext, ToolError, ok_status
@@ -81,6 +86,7 @@ class LLMTool:
         try:
             sp = SamplingParams.from_dict(params)
             sp.validate(1 << 30)
+            check_n(self.llm, sp)
         except (ValueError, TypeError) as e:
             raise ToolError("INVALID_ARGUMENT", str(e))
         if self.lora is not None:
@@ -138,6 +144,8 @@ class LLMTool:
         sp = self._sampling(params)
         if sp.logprobs is not None:
             raise ToolError("INVALID_ARGUMENT", "'logprobs' cannot be combined with function tools")
+        if sp.n > 1:
+            raise ToolError("INVALID_ARGUMENT", "'n' > 1 cannot be combined with function tools")
         try:
             rounds = tool_rounds(params.get("max_tool_rounds"))
         except ValueError as e:
@@ -170,6 +178,10 @@ class LLMTool:
         t0 = time.monotonic()
         prompt = self._prompt(params)
         sp = self._sampling(params)
+        if sp.n > 1:
+            if params.get("return") != "struct":
+                raise ToolError("INVALID_ARGUMENT", "'n' > 1 needs 'return': 'struct' (a string holds one completion)")
+            return await self._run_choices(ctx, params, prompt, sp, t0)
         toks: List[int] = []
         lps: Optional[list] = [] if sp.logprobs is not None else None
         last = None
@@ -197,6 +209,34 @@ class LLMTool:
             resp.string_output = text
         return resp
 
+    async def _run_choices(self, ctx: RequestContext, params: dict, prompt: List[int], sp: SamplingParams,
+                           t0: float) -> "proto.ExecuteToolResponse":
+        """Unary struct answer of an n > 1 request: today's summary for index 0 plus ``choices``."""
+        try:
+            all_toks, lasts = await self.llm.generate_choices(prompt, sp, request_id=ctx.request_id)
+        except ValueError as e:  # refused by the engine itself (n above a remote engine's max_num_seqs)
+            raise ToolError("INVALID_ARGUMENT", str(e))
+        with_ids = bool(params.get("return_token_ids"))
+        choices = []
+        for i, (toks, last) in enumerate(zip(all_toks, lasts)):
+            text = self.tok.decode(toks)
+            cut = self._stop_hit(text, sp.stop)
+            c = {"index": i, "text": text if cut is None else text[:cut],
+                 "finish_reason": last.finish_reason if last is not None else "abort"}
+            if with_ids:
+                c["token_ids"] = list(toks)
+            if sp.logprobs is not None:
+                c["logprobs"] = lpf.struct_block(toks, (last.logprobs if last is not None else None) or [])
+            choices.append(c)
+        lps0 = ((lasts[0].logprobs if lasts[0] is not None else None) or []) if sp.logprobs is not None else None
+        out = self._summary(choices[0]["text"], len(prompt), all_toks[0], lasts[0], t0, with_ids, lps0, sp.lora)
+        n_out = sum(len(t) for t in all_toks)
+        out["usage"] = {"prompt_tokens": len(prompt), "completion_tokens": n_out, "total_tokens": len(prompt) + n_out}
+        out["choices"] = choices
+        resp = proto.ExecuteToolResponse(status=_status())
+        resp.struct_output.update(out)
+        return resp
+
     async def stream(self, ctx: RequestContext, params: dict, secret, metadata: Dict[str, str]):
         tc = self._tools(params)
         if tc is not None:  # a tool-enabled chat is decided whole: one final message
@@ -205,6 +245,9 @@ class LLMTool:
         t0 = time.monotonic()
         prompt = self._prompt(params)
         sp = self._sampling(params)
+        if sp.n > 1:
+            raise ToolError("INVALID_ARGUMENT", "'n' > 1 is not supported on ExecuteToolStream (use ExecuteTool "
+                                                "with 'return': 'struct')")
         toks: List[int] = []
         lps: Optional[list] = [] if sp.logprobs is not None else None
         last = None
@@ -265,6 +308,9 @@ class ReplicaPool:
 
     async def generate_all(self, prompt_ids, params, request_id=None):
         return await self._pick().generate_all(prompt_ids, params, request_id)
+
+    async def generate_choices(self, prompt_ids, params, request_id=None):
+        return await self._pick().generate_choices(prompt_ids, params, request_id)  # one replica runs all n
 
     def healthy(self) -> bool:
         return all(r.healthy() for r in self.replicas)

@@ -31,6 +31,13 @@ to ``guided_json``) constrain the completion on the GPU (engine/grammar.py, ops/
 unsupported pattern or schema keyword is a 400 carrying the compiler's message.
 ``response_format: {"type": "json_object"}`` is ignored.  A completion cut by ``max_tokens``
 (``finish_reason: "length"``) may be a prefix of a match.
+
+Parallel sampling: ``n`` (1..16 and at most the engine's ``max_num_seqs``; anything else is a 400) on
+both endpoints answers with n ``choices`` ordered by ``index``, each with its own ``finish_reason``,
+``logprobs`` and stop-string cut; ``usage.prompt_tokens`` counts the prompt once and
+``completion_tokens`` sums the choices.  Streamed chunks carry their choice's ``index`` (chat: one role
+chunk per index), every index gets exactly one chunk with a ``finish_reason``, and ``usage`` rides the
+last of them.  ``n > 1`` cannot be combined with function tools (400): a tool chat is multi-round.
 """
 
 
@@ -40,14 +47,14 @@ import time
 import uuid
 from typing import Any, Dict, List, Optional
 
-from ..engine.sequence import SamplingParams
+from ..engine.sequence import SamplingParams, check_n
 from ..service import logprob_format as lpf
 from ..service.base import ToolError
 from ..service.tool_calls import run_chat, tool_rounds, validate_tools
 
 _SAMPLING_KEYS = ("max_tokens", "temperature", "top_p", "top_k", "min_p", "seed", "stop", "ignore_eos",
                   "stop_token_ids", "cache_salt", "repetition_penalty", "frequency_penalty", "presence_penalty",
-                  "logit_bias", "guided_regex", "guided_choice", "guided_json", "speculative")
+                  "logit_bias", "guided_regex", "guided_choice", "guided_json", "speculative", "n")
 
 
 
@@ -56,6 +63,7 @@ def _usage(n_prompt: int, n_out: int, metrics) -> dict:
     from the prefix cache (engine/scheduler.py)."""
     return {"prompt_tokens": n_prompt, "completion_tokens": n_out, "total_tokens": n_prompt + n_out,
             "prompt_tokens_details": {"cached_tokens": int((metrics or {}).get("cached_prompt_tokens") or 0)}}
+
 
 def _llm(router, model: Optional[str]):
     """The AsyncLLM serving ``model`` (the ``llm.chat`` tool registered for it)."""
@@ -129,6 +137,7 @@ def create_app(router):
             llm, model = _llm(router, body.get("model"))
             sp = _params(body, chat)
             sp.lora = _lora(router, body.get("model"))
+            check_n(llm, sp)
         except ToolError as e:
             return err(404 if e.code == "NOT_FOUND" else 503, e.message)
         except (ValueError, TypeError) as e:
@@ -145,6 +154,8 @@ def create_app(router):
             if tools and choice != "none":
                 if sp.logprobs is not None:
                     return err(400, "'logprobs' cannot be combined with function tools")
+                if sp.n > 1:
+                    return err(400, "'n' > 1 cannot be combined with function tools")
                 return await _run_tools(body, llm, model, msgs, sp, tools, choice)
             prompt_ids = tok.encode(tok.apply_chat_template(msgs))
         else:
@@ -162,64 +173,87 @@ def create_app(router):
         if body.get("stream"):
             async def sse():
                 from ..engine.tokenizer import IncrementalDetokenizer
-                toks: List[int] = []
-                detok = IncrementalDetokenizer(tok)
-                finish = None
+                n = sp.n
+                toks: List[List[int]] = [[] for _ in range(n)]
+                detoks = [IncrementalDetokenizer(tok) for _ in range(n)]
+                finish: List[Optional[str]] = [None] * n
                 final_metrics = None
-                offset = 0  # completions: text_offset of the next token
+                offset = [0] * n  # completions: text_offset of the next token
+                left, last_index = n, 0
+                chunk_obj = obj + (".chunk" if chat else "")
+
+                def chunk(choice, **kw):
+                    ch = {"id": rid, "object": chunk_obj, "created": created, "model": model, "choices": [choice], **kw}
+                    return f"data: {json.dumps(ch)}\n\n"
+
+                def finish_choice(i):
+                    return ({"index": i, "delta": {}, "finish_reason": finish[i]} if chat
+                            else {"index": i, "text": "", "finish_reason": finish[i]})
+
                 if chat:
-                    first = {"id": rid, "object": "chat.completion.chunk", "created": created, "model": model,
-                             "choices": [{"index": 0, "delta": {"role": "assistant"}, "finish_reason": None}]}
-                    yield f"data: {json.dumps(first)}\n\n"
+                    for i in range(n):
+                        yield chunk({"index": i, "delta": {"role": "assistant"}, "finish_reason": None})
                 agen = llm.generate(prompt_ids, sp, request_id=rid)
                 try:
                     async for out in agen:
-                        toks.extend(out.new_token_ids)
-                        finish = out.finish_reason
-                        final_metrics = out.metrics or final_metrics
-                        delta = detok.push(out.new_token_ids)
+                        i = out.index
+                        toks[i].extend(out.new_token_ids)
+                        finish[i] = out.finish_reason
+                        if i == 0 or final_metrics is None:
+                            final_metrics = out.metrics or final_metrics
+                        delta = detoks[i].push(out.new_token_ids)
                         lp = None
                         if sp.logprobs is not None and out.logprobs:
                             if chat:
                                 lp = {"content": lpf.chat_content(tok, out.new_token_ids, out.logprobs)}
                             else:
-                                lp = lpf.completion_block(tok, out.new_token_ids, out.logprobs, offset)
-                                offset += sum(len(t) for t in lp["tokens"])
+                                lp = lpf.completion_block(tok, out.new_token_ids, out.logprobs, offset[i])
+                                offset[i] += sum(len(t) for t in lp["tokens"])
                         if delta or lp is not None:
-                            choice = ({"index": 0, "delta": {"content": delta}, "finish_reason": None} if chat
-                                      else {"index": 0, "text": delta, "finish_reason": None})
+                            choice = ({"index": i, "delta": {"content": delta}, "finish_reason": None} if chat
+                                      else {"index": i, "text": delta, "finish_reason": None})
                             if lp is not None:
                                 choice["logprobs"] = lp
-                            ch = {"id": rid, "object": obj + (".chunk" if chat else ""), "created": created,
-                                  "model": model, "choices": [choice]}
-                            yield f"data: {json.dumps(ch)}\n\n"
+                            yield chunk(choice)
+                        if out.finished:
+                            left -= 1
+                            if left:  # the last choice's finish chunk carries the usage, below
+                                yield chunk(finish_choice(i))
+                            else:
+                                last_index = i
                 finally:
                     await agen.aclose()
-                last_choice = ({"index": 0, "delta": {}, "finish_reason": finish} if chat
-                               else {"index": 0, "text": "", "finish_reason": finish})
-                last = {"id": rid, "object": obj + (".chunk" if chat else ""), "created": created, "model": model,
-                        "choices": [last_choice],
-                        "usage": _usage(len(prompt_ids), len(toks), final_metrics)}
-                yield f"data: {json.dumps(last)}\n\n"
+                yield chunk(finish_choice(last_index),
+                            usage=_usage(len(prompt_ids), sum(len(t) for t in toks), final_metrics))
                 yield "data: [DONE]\n\n"
 
             return StreamingResponse(sse(), media_type="text/event-stream")
 
-        toks, last = await llm.generate_all(prompt_ids, sp, request_id=rid)
-        text = tok.decode(toks)
-        if sp.stop:
-            cuts = [text.find(s) for s in sp.stop if text.find(s) >= 0]
-            if cuts:
-                text = text[:min(cuts)]
-        choice = ({"index": 0, "message": {"role": "assistant", "content": text},
-                   "finish_reason": last.finish_reason if last else None} if chat
-                  else {"index": 0, "text": text, "finish_reason": last.finish_reason if last else None})
-        if sp.logprobs is not None:
-            entries = (last.logprobs if last else None) or []
-            choice["logprobs"] = ({"content": lpf.chat_content(tok, toks, entries)} if chat
-                                  else lpf.completion_block(tok, toks, entries))
-        return {"id": rid, "object": obj, "created": created, "model": model, "choices": [choice],
-                "usage": _usage(len(prompt_ids), len(toks), last.metrics if last else None)}
+        if sp.n > 1:
+            try:
+                all_toks, lasts = await llm.generate_choices(prompt_ids, sp, request_id=rid)
+            except ValueError as e:  # refused by the engine itself (n above a remote engine's max_num_seqs)
+                return err(400, str(e))
+        else:
+            toks, last = await llm.generate_all(prompt_ids, sp, request_id=rid)
+            all_toks, lasts = [toks], [last]
+        choices = []
+        for i, (toks, last) in enumerate(zip(all_toks, lasts)):
+            text = tok.decode(toks)
+            if sp.stop:
+                cuts = [text.find(s) for s in sp.stop if text.find(s) >= 0]
+                if cuts:
+                    text = text[:min(cuts)]
+            choice = ({"index": i, "message": {"role": "assistant", "content": text},
+                       "finish_reason": last.finish_reason if last else None} if chat
+                      else {"index": i, "text": text, "finish_reason": last.finish_reason if last else None})
+            if sp.logprobs is not None:
+                entries = (last.logprobs if last else None) or []
+                choice["logprobs"] = ({"content": lpf.chat_content(tok, toks, entries)} if chat
+                                      else lpf.completion_block(tok, toks, entries))
+            choices.append(choice)
+        return {"id": rid, "object": obj, "created": created, "model": model, "choices": choices,
+                "usage": _usage(len(prompt_ids), sum(len(t) for t in all_toks), lasts[0].metrics if lasts[0] else None)}
 
     async def _run_tools(body, llm, model, msgs, sp, tools, choice):
         rid = "chatcmpl-" + uuid.uuid4().hex[:24]

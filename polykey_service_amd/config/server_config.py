@@ -53,6 +53,8 @@ class ServerConfig:
     num_speculative_tokens: int = 3
     ngram_max: int = 4
     ngram_min: int = 2
+    # parallel sampling (n > 1): fork choice 0's prompt KV for the other choices (False: they prefill it)
+    kv_fork: bool = True
     hip_graphs: bool = True
     device: str = "cuda"
     seed: int = 0
@@ -95,6 +97,7 @@ _ENV = {
     "num_speculative_tokens": "POLYKEY_NUM_SPECULATIVE_TOKENS",
     "ngram_max": "POLYKEY_NGRAM_MAX",
     "ngram_min": "POLYKEY_NGRAM_MIN",
+    "kv_fork": "POLYKEY_KV_FORK",
     "hip_graphs": "POLYKEY_HIP_GRAPHS",
     "device": "POLYKEY_DEVICE",
     "seed": "POLYKEY_SEED",

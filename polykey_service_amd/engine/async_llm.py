@@ -66,6 +66,7 @@ class AsyncLLM:
         # requests submitted by another process's front end (engine/remote.py EngineServer):
         # their outputs go to the external sink, called on the engine thread once per step
         self._external: set = set()
+        self._external_left: Dict[str, int] = {}  # n > 1 requests among them: choices still running
         self._external_sink: Optional[Callable[[list], None]] = None
         self._lock = threading.Lock()
         self._stop = False
@@ -123,6 +124,8 @@ class AsyncLLM:
             return
         with self._lock:
             self._external.add(rid)
+            if isinstance(params.n, int) and params.n > 1:
+                self._external_left[rid] = params.n  # choices still running
             self._cmds.append(("add", (rid, prompt_ids, params)))
         self._wake.set()
 
@@ -131,6 +134,7 @@ class AsyncLLM:
             if rid not in self._external:
                 return
             self._external.discard(rid)
+            self._external_left.pop(rid, None)
             self._cmds.append(("abort", rid))
         self._wake.set()
 
@@ -148,26 +152,34 @@ class AsyncLLM:
             self._cmds.append(("add", (rid, prompt_ids, params)))
         self._wake.set()
         finished = False
+        left = params.n if isinstance(params.n, int) and params.n > 1 else 1  # choices still running
+        held = None  # an output of another choice met while coalescing: delivered next
         try:
             while True:
-                item = await q.get()
+                item, held = (held, None) if held is not None else (await q.get(), None)
                 # coalesce whatever else already arrived: a lagging consumer gets one message
-                # carrying several tokens instead of one message per engine step
+                # carrying several tokens instead of one message per engine step (outputs of one
+                # choice only: the stream of an n > 1 request interleaves its choices)
                 while not isinstance(item, BaseException) and not item.finished and not q.empty():
                     nxt = q.get_nowait()
                     if isinstance(nxt, BaseException):
                         item = nxt
                         break
+                    if nxt.index != item.index:
+                        held = nxt
+                        break
                     item = RequestOutput(item.request_id, item.new_token_ids + nxt.new_token_ids, nxt.finished,
                                          nxt.finish_reason, nxt.num_prompt_tokens, nxt.num_output_tokens,
-                                         nxt.metrics,
-                                         None if item.logprobs is None else item.logprobs + (nxt.logprobs or []))
+                                         nxt.metrics, index=nxt.index,
+                                         logprobs=None if item.logprobs is None else item.logprobs + (nxt.logprobs or []))
                 if isinstance(item, BaseException):
                     finished = True
                     raise item
-                yield item
                 if item.finished:
-                    finished = True
+                    left -= 1
+                    finished = left == 0
+                yield item
+                if finished:
                     return
         finally:
             with self._lock:
@@ -192,6 +204,12 @@ class AsyncLLM:
         if last is not None and lps is not None:
             last = dataclasses.replace(last, logprobs=lps)
         return toks, last
+
+    async def generate_choices(self, prompt_ids: List[int], params: SamplingParams,
+                               request_id: Optional[str] = None) -> Tuple[List[List[int]], List[RequestOutput]]:
+        """``generate_all`` for a request with ``params.n`` choices → (token ids per index, last output
+        per index, each with the logprob entries of all its tokens when the request asked for them)."""
+        return await collect_choices(self.generate(prompt_ids, params, request_id), params.n)
 
     def shutdown(self, timeout: Optional[float] = None) -> None:
         """Stop the engine thread (DP attention + EP: waits until every rank has asked to stop,
@@ -295,8 +313,16 @@ class AsyncLLM:
             for rid, item in items:
                 if rid in self._external:
                     external.append((rid, item))
-                    if isinstance(item, BaseException) or item.finished:
+                    if isinstance(item, BaseException):
+                        self._external_left.pop(rid, None)
                         self._external.discard(rid)
+                    elif item.finished:
+                        left = self._external_left.get(rid, 1) - 1  # an n > 1 request ends with its last choice
+                        if left > 0:
+                            self._external_left[rid] = left
+                        else:
+                            self._external_left.pop(rid, None)
+                            self._external.discard(rid)
                     continue
                 ent = self._streams.get(rid)
                 if ent is not None:
@@ -381,6 +407,21 @@ class AsyncLLM:
         finally:
             if prof is not None:
                 prof.stop()
+
+
+async def collect_choices(stream, n: int) -> Tuple[List[List[int]], List[RequestOutput]]:
+    """Drain a request's output stream into per-index token lists and last outputs."""
+    toks: List[List[int]] = [[] for _ in range(n)]
+    lps: List[Optional[list]] = [None] * n
+    last: List[Optional[RequestOutput]] = [None] * n
+    async for out in stream:
+        i = out.index
+        toks[i].extend(out.new_token_ids)
+        if out.logprobs is not None:
+            lps[i] = (lps[i] or []) + out.logprobs
+        last[i] = out
+    return toks, [o if o is None or lps[i] is None else dataclasses.replace(o, logprobs=lps[i])
+                  for i, o in enumerate(last)]
 
 
 def _fanout(batch) -> None:

@@ -79,6 +79,10 @@ class EngineConfig:
     num_speculative_tokens: int = 3
     ngram_max: int = 4
     ngram_min: int = 2
+    # parallel sampling (README "Parallel sampling"): choices 1 .. n-1 of an n > 1 request take choice
+    # 0's prompt KV by a fork (shared full blocks, one copied partial block) instead of prefilling
+    # it again; False / POLYKEY_KV_FORK=0: they prefill it themselves (prefix cache as usual)
+    kv_fork: bool = dataclasses.field(default_factory=lambda: os.environ.get("POLYKEY_KV_FORK", "1") != "0")
 
     @classmethod
     def from_server_config(cls, sc) -> "EngineConfig":
@@ -92,7 +96,8 @@ class EngineConfig:
                    max_lora_rank=getattr(sc, "max_lora_rank", 64),
                    speculative=getattr(sc, "speculative", "") or None,
                    num_speculative_tokens=getattr(sc, "num_speculative_tokens", 3),
-                   ngram_max=getattr(sc, "ngram_max", 4), ngram_min=getattr(sc, "ngram_min", 2))
+                   ngram_max=getattr(sc, "ngram_max", 4), ngram_min=getattr(sc, "ngram_min", 2),
+                   kv_fork=bool(getattr(sc, "kv_fork", True)) and os.environ.get("POLYKEY_KV_FORK", "1") != "0")
 
 
 def tokenizer_for(cfg: EngineConfig, mcfg: Optional[ModelConfig] = None):
@@ -250,6 +255,13 @@ class LLMEngine:
         self.proposer: Optional[spec.Proposer] = None
         self.spec_k = 0
         self.spec_steps = self.spec_draft_tokens = self.spec_accepted_tokens = 0
+        # parallel sampling: the fork needs every rank to copy, and workers have no fork message.
+        # Counters, taken when the choices are released: n > 1 requests whose choices were forked,
+        # requests with a choice released without a fork (no block, fork off, TP / EP), prompt tokens
+        # the forked choices were handed.  A forked choice that loses its blocks again before it first
+        # runs (Scheduler._unmatch) is counted by the scheduler's num_unforked / num_unforked_tokens
+        self.kv_fork = cfg.kv_fork and self.st.tp_size == 1 and self.st.ep_size == 1 and not self.lockstep
+        self.kv_forks = self.kv_fork_fallbacks = self.kv_fork_shared_tokens = 0
         if cfg.speculative:
             self.spec_k = cfg.num_speculative_tokens
             self.proposer = spec.NgramProposer(cfg.ngram_max, cfg.ngram_min)
@@ -334,21 +346,32 @@ class LLMEngine:
         if params.lora is not None and params.lora not in self.lora_names:
             raise ValueError(f"unknown LoRA adapter {params.lora!r}: this engine serves "
                              f"{', '.join(self.lora_names) if self.lora_names else 'no adapters'}")
+        if params.n > self.cfg.max_num_seqs:
+            raise ValueError(f"n must be at most max_num_seqs ({self.cfg.max_num_seqs}), got {params.n}")
         g = self._grammar(params)
-        seq = Sequence(request_id or uuid.uuid4().hex, prompt_ids, params, self.mcfg.eos_token_id, user)
-        if self.spec_k:
-            seq.spec_drafted = seq.spec_accepted = 0
-        if g is None:
-            self.scheduler.add(seq)
-            return seq
-        seq.grammar = g
-        self.runner.acquire_grammar(seq)
+        rid = request_id or uuid.uuid4().hex
+        # parallel sampling: all n choices exist from here; choice 0 is queued, the others are parked
+        # behind it until its prompt is computed (_fork).  -> choice 0 (``.choices`` holds them all)
+        seqs = [Sequence(rid, prompt_ids, params, self.mcfg.eos_token_id, user, index=i) for i in range(params.n)]
+        for seq in seqs:
+            if params.n > 1:
+                seq.choices = seqs
+            if self.spec_k:
+                seq.spec_drafted = seq.spec_accepted = 0
+            seq.grammar = g
         try:
-            self.scheduler.add(seq)
+            if g is not None:  # the choices share the table; each holds its own reference to it
+                for seq in seqs:
+                    self.runner.acquire_grammar(seq)
+            for seq in seqs:
+                self.scheduler.add(seq, behind=seqs[0] if seq.index else None)
         except Exception:
-            self.runner.release_grammar(seq)
+            if self.scheduler.by_request.get(rid) is seqs[0]:
+                self.scheduler.abort(rid)  # the choices already queued
+            for seq in seqs:
+                self.runner.release_grammar(seq)
             raise
-        return seq
+        return seqs[0]
 
     def _grammar(self, params: SamplingParams):
         """The compiled constraint of a guided request (from the LRU), checked against this
@@ -538,6 +561,7 @@ class LLMEngine:
             while n_acc < len(d) and row[n_acc] == d[n_acc]:
                 n_acc += 1
             s.num_computed += 1 + n_acc
+            self._fork_if_prompt_done(s)
             s.spec_drafted += len(d)
             s.spec_accepted += n_acc
             self.spec_draft_tokens += len(d)
@@ -567,8 +591,12 @@ class LLMEngine:
         for s, n in batch.prefills:
             s.num_computed += n
             self.scheduler.commit_prefix(s)  # the step that wrote these blocks' KV has completed
+            self._fork_if_prompt_done(s)
         for s in batch.decodes:
             s.num_computed += 1
+            # (a prompt's last token runs as a decode row when one token is pending: a one-token
+            # prompt, or a chunked prefill whose last chunk is one token)
+            self._fork_if_prompt_done(s)
         done = []
         for r, (s, tok) in enumerate(zip(sampling, toks)):
             if s.is_finished():  # aborted while its step was in flight
@@ -584,11 +612,46 @@ class LLMEngine:
         self.total_output_tokens += len(toks)
         return done
 
+    def _fork_if_prompt_done(self, s: Sequence) -> None:
+        """After ``s.num_computed`` advanced and before the step's token is appended (``s`` may finish
+        in this very step): release the choices parked behind ``s`` once its prompt is computed,
+        whichever list of the batch its last prompt token ran in."""
+        if self.scheduler.parked and s.seq_id in self.scheduler.parked and s.num_computed >= len(s.prompt_ids):
+            self._fork(s)
+
+    def _fork(self, leader: Sequence) -> None:
+        """Choice 0's prompt is computed: its parked siblings take the KV of its first P - 1 tokens --
+        the (P - 1) // bs full blocks by reference, the partial block (if any) by one copy launch for
+        all of them -- and go to the front of ``waiting`` with one pending token: each recomputes the
+        last prompt token as a one-row step and samples its own first token there.  Shared blocks
+        are never written again (every later write is at a position >= P - 1, in the private block or
+        beyond); the copied block's bytes beyond slot (P - 1) % bs are overwritten before any read.
+        A choice the pool cannot grant its block, or an engine without the fork (kv_fork off, TP /
+        EP), leaves the choices plain waiting sequences: full prefill, prefix cache as usual."""
+        m = len(leader.prompt_ids) - 1
+        pairs, forked = [], 0
+        parked = self.scheduler.release_parked(leader)  # (an aborted request has none left)
+        if self.kv_fork and m > 0:
+            for c in parked:
+                got = self.bm.fork(leader.seq_id, c.seq_id, m)
+                if got is None:
+                    break  # no free block: this choice and the rest prefill
+                pairs += got
+                c.num_computed = c.forked_tokens = m
+                forked += 1
+        if pairs:
+            self.runner.copy_kv_blocks(pairs)
+        if forked:
+            self.kv_forks += 1
+            self.kv_fork_shared_tokens += forked * m
+        if forked < len(parked):
+            self.kv_fork_fallbacks += 1
+
     @staticmethod
     def _outputs(done) -> List[RequestOutput]:
         return [RequestOutput(s.request_id, toks, reason is not None, reason.value if reason else None,
                               len(s.prompt_ids), len(s.output_ids), seq_metrics(s) if reason else None,
-                              s.logprobs[-len(toks):] if s.logprobs is not None else None)
+                              index=s.index, logprobs=s.logprobs[-len(toks):] if s.logprobs is not None else None)
                 for s, toks, reason in done]
 
     def generate(self, prompts: List[List[int]], params: SamplingParams) -> List[List[int]]:

@@ -37,6 +37,7 @@ from ..ops import attention as attn_ops
 from ..ops import gemm
 from ..ops import native
 from ..ops import grammar as gram_ops
+from ..ops import kv as kv_ops
 from ..ops import penalties as pen_ops
 from ..ops import sampler as sampler_ops
 from .scheduler import ScheduledBatch
@@ -282,7 +283,16 @@ class ModelRunner:
             k = torch.zeros((num_blocks, a.nkv, self.bs, a.hd), dtype=raw, device=self.device).view(dt)
             v = torch.zeros((num_blocks, a.nkv, a.hd, self.bs), dtype=raw, device=self.device).view(dt)
             self.kv_caches.append((k, v))
+        self.kv_ptr_table = kv_ops.pointer_table(self.kv_caches)  # the block copy's 2 x layers base pointers
         return num_blocks
+
+    def copy_kv_blocks(self, pairs) -> None:
+        """Block dst := block src in K and V of every layer for the (src, dst) pairs of a prompt fork
+        (LLMEngine._fork): one eager launch on the stream the steps run on, ordered after the
+        prefill that wrote the sources and before the step that reads the copies; no host wait,
+        never captured."""
+        kv_ops.copy_blocks(self.kv_caches, pairs, self.kv_ptr_table)  # n <= 16: at most 15 pairs
+        self.stats["kv_copy_launches"] = self.stats.get("kv_copy_launches", 0) + 1
 
     def activation_reserve_bytes(self) -> int:
         m = self.mcfg
@@ -477,7 +487,7 @@ class ModelRunner:
         if slot is not None:
             self._pen_free.append(slot)
         live = self.live_requests
-        if seq.is_finished() or (live is not None and live.get(seq.request_id) is not seq):
+        if seq.is_finished() or (live is not None and live.get(seq.key) is not seq):
             self.release_grammar(seq)
 
     # ------------------------------------------------------------------ guided decoding

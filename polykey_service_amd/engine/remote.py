@@ -9,7 +9,10 @@ Wire format: 4-byte little-endian length + a msgpack map per frame.
     front end -> engine   {"op": "add", "rid", "prompt": [ids], "params": {...}, "final": bool}
                           {"op": "abort", "rid"}      {"op": "stop"}
     engine -> front end   {"op": "out", "items": [[rid, new_ids, finished, reason, n_prompt, n_out,
-                                                   metrics | null, error | null], ...]}
+                                                   metrics | null, error | null, logprobs | null
+                                                   (, choice index when it is not 0)], ...]}
+A request with n > 1 choices (parallel sampling) carries "n" in its params and its items carry the choice
+index as a tenth element when it is not 0; frames of n = 1 requests are byte for byte what they were.
 One "out" frame carries every request's news of one engine step (written by the engine thread
 itself, no event loop in between); a request submitted with ``final`` (unary RPCs without stop
 strings) is reported once, with all its tokens, when it finishes.
@@ -61,6 +64,8 @@ def _params_dict(p: SamplingParams) -> dict:
     d["stop_token_ids"] = list(d["stop_token_ids"])
     d["stop"] = list(d["stop"])
     d["logit_bias"] = [[int(t), float(b)] for t, b in d["logit_bias"]]  # pairs: msgpack refuses integer map keys
+    if d["n"] == 1:
+        del d["n"]  # an n = 1 frame stays what it was
     return d
 
 
@@ -85,6 +90,8 @@ class EngineServer:
         self._owner: Dict[str, int] = {}   # rid -> connection that submitted it
         self._final: Dict[str, List] = {}  # rid -> tokens so far (final-only requests)
         self._final_lp: Dict[str, List] = {}  # rid -> their logprob entries so far (when requested)
+        # n > 1 requests: choices still running; their choices i > 0 accumulate under (rid, i)
+        self._left: Dict[str, int] = {}
 
     def _sink(self, items) -> None:
         """Engine thread: one frame per front end with this step's outputs of its requests."""
@@ -93,30 +100,41 @@ class EngineServer:
             for rid, o in items:
                 cid = self._owner.get(rid)
                 if isinstance(o, BaseException):
-                    self._final.pop(rid, None)
-                    self._final_lp.pop(rid, None)
-                    self._owner.pop(rid, None)
-                    per.setdefault(cid, []).append([rid, [], True, "error", 0, 0, None, str(o), None])
+                    # an n > 1 request the engine refused at add_request (n above its max_num_seqs, which
+                    # a remote front end cannot see): "invalid", so that the front end answers 400 /
+                    # INVALID_ARGUMENT; every other error frame is what it was
+                    reason = "invalid" if isinstance(o, ValueError) and rid in self._left else "error"
+                    self._forget(rid)
+                    per.setdefault(cid, []).append([rid, [], True, reason, 0, 0, None, str(o), None])
                     continue
-                acc = self._final.get(rid)
+                key = rid if o.index == 0 else (rid, o.index)
+                acc = self._final.get(key)
+                if acc is None and o.index and rid in self._final:
+                    acc = self._final[key] = []
                 lps = o.logprobs
                 if acc is not None:
                     acc.extend(o.new_token_ids)
                     if lps is not None:
-                        self._final_lp.setdefault(rid, []).extend(lps)
+                        self._final_lp.setdefault(key, []).extend(lps)
                     if not o.finished:
                         continue
-                    del self._final[rid]
                     ids = acc
-                    lps = self._final_lp.pop(rid, None)
+                    lps = self._final_lp.pop(key, None)
+                    if o.index:
+                        del self._final[key]
                 else:
                     ids = o.new_token_ids
                 if o.finished:
-                    self._owner.pop(rid, None)
-                per.setdefault(cid, []).append([rid, list(ids), o.finished, o.finish_reason, o.num_prompt_tokens,
-                                                o.num_output_tokens, o.metrics, None,
-                                                None if lps is None else [[lp, [list(t) for t in top]]
-                                                                          for lp, top in lps]])
+                    left = self._left.get(rid, 1) - 1
+                    if left > 0:
+                        self._left[rid] = left
+                    else:
+                        self._forget(rid)
+                item = [rid, list(ids), o.finished, o.finish_reason, o.num_prompt_tokens, o.num_output_tokens,
+                        o.metrics, None, None if lps is None else [[lp, [list(t) for t in top]] for lp, top in lps]]
+                if o.index:
+                    item.append(o.index)
+                per.setdefault(cid, []).append(item)
             conns = {cid: self._conns.get(cid) for cid in per}
         for cid, out in per.items():
             c = conns.get(cid)
@@ -126,6 +144,16 @@ class EngineServer:
                 _send(c[0], c[1], {"op": "out", "items": out})
             except OSError:
                 pass  # front end gone: its reader sees the closed connection and stops
+
+    def _forget(self, rid: str) -> None:
+        """(under the lock) The engine reports nothing more for ``rid``."""
+        if self._left.pop(rid, None) is not None:  # n > 1: what its other choices accumulated
+            for d in (self._final, self._final_lp):
+                for key in [k for k in d if isinstance(k, tuple) and k[0] == rid]:
+                    del d[key]
+        self._final.pop(rid, None)
+        self._final_lp.pop(rid, None)
+        self._owner.pop(rid, None)
 
     def _accept(self) -> socket.socket:
         """The next connection whose hello frame carries the shared token (others are closed)."""
@@ -151,16 +179,17 @@ class EngineServer:
                     break
                 if msg["op"] == "add":
                     rid = msg["rid"]
+                    params = SamplingParams(**msg["params"])
                     with self._lock:
                         self._owner[rid] = cid
                         if msg.get("final"):
                             self._final[rid] = []
-                    self.llm.submit_external(rid, msg["prompt"], SamplingParams(**msg["params"]))
+                        if isinstance(params.n, int) and params.n > 1:
+                            self._left[rid] = params.n
+                    self.llm.submit_external(rid, msg["prompt"], params)
                 elif msg["op"] == "abort":
                     with self._lock:
-                        self._final.pop(msg["rid"], None)  # the engine reports nothing more for it
-                        self._final_lp.pop(msg["rid"], None)
-                        self._owner.pop(msg["rid"], None)
+                        self._forget(msg["rid"])
                     self.llm.abort_external(msg["rid"])
         except OSError:
             pass
@@ -245,10 +274,13 @@ class RemoteEngine:
                         if ent is None:
                             continue
                         lps = rest[0] if rest else None
+                        index = rest[1] if len(rest) > 1 else 0
                         if lps is not None:
                             lps = [(float(lp), [(int(i), float(v)) for i, v in top]) for lp, top in lps]
-                        item = RuntimeError(err) if err else RequestOutput(rid, ids, fin, reason, npr, nout, metrics,
-                                                                           lps)
+                        if err:  # ("invalid": the engine refused the request itself)
+                            item = ValueError(err) if reason == "invalid" else RuntimeError(err)
+                        else:
+                            item = RequestOutput(rid, ids, fin, reason, npr, nout, metrics, index=index, logprobs=lps)
                         by_loop.setdefault(ent[0], []).append((ent[1], item))
                 for loop, batch in by_loop.items():
                     try:
@@ -289,14 +321,17 @@ class RemoteEngine:
         try:
             _send(self.sock, self._wlock, {"op": "add", "rid": rid, "prompt": list(prompt_ids),
                                            "params": _params_dict(params), "final": bool(final_only)})
+            left = params.n if isinstance(params.n, int) and params.n > 1 else 1  # choices still running
             while True:
                 item = await q.get()
                 if isinstance(item, BaseException):
                     finished = True
                     raise item
-                yield item
                 if item.finished:
-                    finished = True
+                    left -= 1
+                    finished = left == 0
+                yield item
+                if finished:
                     return
         finally:
             with self._lock:
@@ -314,6 +349,11 @@ class RemoteEngine:
             toks.extend(out.new_token_ids)
             last = out  # final-only: the one output carries every token's logprobs too
         return toks, last
+
+    async def generate_choices(self, prompt_ids: List[int], params: SamplingParams, request_id: Optional[str] = None):
+        """``generate_all`` for ``params.n`` choices (AsyncLLM.generate_choices)."""
+        from .async_llm import collect_choices
+        return await collect_choices(self.generate(prompt_ids, params, request_id, final_only=True), params.n)
 
     def shutdown(self, timeout: Optional[float] = None) -> None:
         if self._closed:

@@ -24,6 +24,12 @@ admitted with nothing computed first takes the cached blocks matching the longes
 its tokens (chained block hashes) and starts its prefill after them — leaving at least two
 tokens to compute, so it still runs a prefill that samples.  The engine registers a prefill's
 full blocks (:meth:`Scheduler.commit_prefix`) once the step that wrote their KV completed.
+
+Parallel sampling (``SamplingParams.n > 1``): choices 1 .. n-1 of a request are *parked* behind choice
+0 and enter ``waiting`` (at its front) when choice 0's prompt is computed -- forked, i.e. already
+owning blocks with ``num_computed = P - 1`` and one pending token, which is admitted as a decode row,
+or plain (LLMEngine._fork).  A waiting sequence that owns blocks hands them back on abort, on a
+failed admission and when a running sequence is preempted.
 """
 from __future__ import annotations
 
@@ -106,12 +112,20 @@ class Scheduler:
         self._decode_stall = 0
         self.waiting: Deque[Sequence] = collections.deque()
         self.running: List[Sequence] = []
-        self.by_request: Dict[str, Sequence] = {}
+        self.by_request: Dict[object, Sequence] = {}  # Sequence.key -> live sequence
+        # parallel sampling (n > 1): choices 1 .. n-1 wait here, keyed by choice 0's seq id, until the
+        # step that completes choice 0's prompt (LLMEngine._fork releases them to the front of
+        # `waiting`, forked or not); `groups` holds every choice of a live n > 1 request for abort
+        self.parked: Dict[int, List[Sequence]] = {}
+        self.groups: Dict[str, List[Sequence]] = {}
         self.num_preemptions = 0
         self.prefix_caching = bool(getattr(block_manager, "prefix_caching", False))
         # seq_id -> (chained block hashes, prompt tokens) at admission
         self._hashes: Dict[int, Tuple[np.ndarray, np.ndarray]] = {}
         self.num_cached_tokens = 0  # prompt tokens served from the prefix cache
+        # forked choices that handed their blocks back before they first ran, and the tokens they
+        # then prefilled after all (the engine's fork counters are taken at fork time)
+        self.num_unforked = self.num_unforked_tokens = 0
         # called with the sequence at every exit that frees its blocks (finish, abort, both
         # preemption paths): the runner releases per-sequence device state (its penalty slot)
         self.on_free: Optional[Callable[[Sequence], None]] = None
@@ -122,7 +136,9 @@ class Scheduler:
             self.on_free(seq)
 
     # --------------------------------------------------------------- queue ops
-    def add(self, seq: Sequence) -> None:
+    def add(self, seq: Sequence, behind: Optional[Sequence] = None) -> None:
+        """Queue ``seq``; with ``behind`` (choice 0 of its request) park it until that one's prompt
+        is computed instead."""
         if seq.num_tokens + seq.params.max_tokens > self.max_model_len + 1:
             # fail fast instead of overflowing the block table mid-generation
             room = self.max_model_len - seq.num_tokens
@@ -135,13 +151,30 @@ class Scheduler:
         if seq.params.max_tokens > cap:
             # a lone sequence must always be able to finish, or preemption would livelock
             seq.params = dataclasses.replace(seq.params, max_tokens=cap)
-        self.waiting.append(seq)
-        self.by_request[seq.request_id] = seq
+        if behind is None:
+            self.waiting.append(seq)
+        else:
+            self.parked.setdefault(behind.seq_id, []).append(seq)
+        self.by_request[seq.key] = seq
+        if seq.choices is not None:
+            self.groups[seq.request_id] = seq.choices
 
     def abort(self, request_id: str) -> Optional[Sequence]:
-        seq = self.by_request.pop(request_id, None)
-        if seq is None:
-            return None
+        """Abort every live choice of the request; -> its first live choice (None: nothing was live)."""
+        group = self.groups.pop(request_id, None)
+        if group is None:
+            seq = self.by_request.get(request_id)
+            group = [] if seq is None else [seq]
+        first = None
+        for seq in group:
+            if self.by_request.get(seq.key) is not seq:
+                continue  # this choice has finished
+            self._abort_one(seq)
+            first = first or seq
+        return first
+
+    def _abort_one(self, seq: Sequence) -> None:
+        del self.by_request[seq.key]
         if seq in self.running:
             self.running.remove(seq)
         else:
@@ -149,12 +182,12 @@ class Scheduler:
                 self.waiting.remove(seq)
             except ValueError:
                 pass
-        self._free(seq)
+        self.parked.pop(seq.seq_id, None)  # choice 0: the others are aborted with it
+        self._free(seq)  # (a waiting sequence may own blocks: a forked choice, a prefix match)
         self._hashes.pop(seq.seq_id, None)
         seq.status = SeqStatus.FINISHED
         seq.finish_reason = FinishReason.ABORT
         seq.finish_time = time.monotonic()
-        return seq
 
     def finish(self, seq: Sequence, reason: FinishReason) -> None:
         seq.status = SeqStatus.FINISHED
@@ -162,16 +195,24 @@ class Scheduler:
         seq.finish_time = time.monotonic()
         self._free(seq)
         self._hashes.pop(seq.seq_id, None)
-        self.by_request.pop(seq.request_id, None)
+        self.by_request.pop(seq.key, None)
+        if seq.choices is not None and all(c.is_finished() for c in seq.choices):
+            self.groups.pop(seq.request_id, None)
+
+    def release_parked(self, leader: Sequence) -> List[Sequence]:
+        """The parked choices of ``leader``'s request go to the front of ``waiting``, in index order."""
+        parked = self.parked.pop(leader.seq_id, [])
+        self.waiting.extendleft(reversed(parked))
+        return parked
 
     def remove_finished(self) -> None:
         self.running = [s for s in self.running if s.status != SeqStatus.FINISHED]
 
     def has_work(self) -> bool:
-        return bool(self.waiting or self.running)
+        return bool(self.waiting or self.running or self.parked)
 
     def num_unfinished(self) -> int:
-        return len(self.waiting) + len(self.running)
+        return len(self.waiting) + len(self.running) + sum(len(p) for p in self.parked.values())
 
     # ------------------------------------------------------------ prefix cache
     def _match_prefix(self, seq: Sequence) -> None:
@@ -187,10 +228,26 @@ class Scheduler:
         seq.num_computed = got * bs
 
     def _unmatch(self, seq: Sequence) -> None:
-        """Admission failed after a match: hand the blocks back (they stay cached)."""
-        if self.prefix_caching and seq.num_computed and self.bm.has(seq.seq_id):
+        """Admission failed after a match, or for a forked choice: hand the blocks back (matched ones
+        stay cached; the choice becomes a plain waiting sequence).  Safe without prefix caching too:
+        a waiting sequence has ``num_computed > 0`` and blocks only after a prefix match made in this
+        very admission attempt or after a fork (a preempted one is reset to 0 and owns none)."""
+        if seq.num_computed and self.bm.has(seq.seq_id):
             self._free(seq)
             seq.num_computed = 0
+            if seq.forked_tokens and seq.first_scheduled is None:  # the fork never ran
+                self.num_unforked += 1
+                self.num_unforked_tokens += seq.forked_tokens
+                seq.forked_tokens = 0
+
+    def _release_waiting(self) -> None:
+        """A running sequence was preempted for want of blocks: waiting sequences that own blocks
+        (forked choices not yet admitted) hand them back, or the preempted one might never return.
+        All of them, whoever was preempted: the pool is short, a forked choice waits one step at
+        most before it is admitted, and the ones stripped here usually re-match their full blocks
+        through the prefix cache."""
+        for seq in self.waiting:
+            self._unmatch(seq)
 
     def commit_prefix(self, seq: Sequence) -> None:
         """Register the sequence's full blocks whose KV is now in the cache."""
@@ -211,6 +268,7 @@ class Scheduler:
         cand.status = SeqStatus.WAITING
         cand.num_preemptions += 1
         self.num_preemptions += 1
+        self._release_waiting()
         self.waiting.appendleft(cand)
         return cand
 
@@ -263,6 +321,7 @@ class Scheduler:
             seq.status = SeqStatus.WAITING
             seq.num_preemptions += 1
             self.num_preemptions += 1
+            self._release_waiting()
             self.waiting.appendleft(seq)
             st.preempted.append(seq)
         # preempted sequences that were already scheduled this step are dropped from it
@@ -294,7 +353,8 @@ class Scheduler:
                 # cache hits count once per request: a preempted sequence re-admitted later
                 # re-matches its own committed blocks (prompt + output), which is no hit
                 seq.first_scheduled = time.monotonic()
-                seq.num_cached_tokens = min(seq.num_computed, len(seq.prompt_ids))
+                # (a forked choice's tokens came from its request's own prefill: no cache hit either)
+                seq.num_cached_tokens = 0 if seq.forked_tokens else min(seq.num_computed, len(seq.prompt_ids))
                 self.num_cached_tokens += seq.num_cached_tokens
             # `running` stays in arrival order (seq ids are monotonic): a re-admitted preempted
             # sequence keeps its age, so "youngest" in _preempt_youngest is the latest arrival

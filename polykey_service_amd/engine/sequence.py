@@ -13,6 +13,7 @@ from typing import List, Optional, Sequence as Seq
 MAX_LOGPROBS = 20  # longest top_logprobs list (the logprobs kernel's compile-time constant)
 MAX_GUIDED_STOP_IDS = 16  # plus eos: the 17 end ids of a grammar slot (ops/grammar.py)
 MAX_LOGIT_BIAS = 300  # longest logit_bias list (the penalty kernels' per-slot table, ops/penalties.py)
+MAX_N = 16  # most choices of one request (parallel sampling): one fork fits one copy launch
 
 
 def _norm_logit_bias(v) -> tuple:
@@ -63,6 +64,9 @@ class SamplingParams:
     # speculative decoding (engine/spec.py): None = the engine's setting, False = never draft for this
     # request; True on an engine without speculation is ignored
     speculative: Optional[bool] = None
+    # parallel sampling: the request yields n choices, index 0 .. n-1, each an ordinary sequence with
+    # these parameters (choice i samples with seed + i); 1 .. MAX_N and at most the engine's max_num_seqs
+    n: int = 1
 
     @property
     def has_penalties(self) -> bool:
@@ -78,6 +82,8 @@ class SamplingParams:
             raise ValueError("max_tokens must be >= 1")
         if self.temperature < 0:
             raise ValueError("temperature must be >= 0")
+        if isinstance(self.n, bool) or not isinstance(self.n, int) or not 1 <= self.n <= MAX_N:
+            raise ValueError(f"n must be an integer in [1, {MAX_N}]")
         if not 0 < self.top_p <= 1:
             raise ValueError("top_p must be in (0, 1]")
         if self.top_k < 0:
@@ -150,6 +156,10 @@ class SamplingParams:
                     v = _norm_logit_bias(v)
                 elif f.name == "seed":
                     v = int(v)
+                elif f.name == "n":
+                    if isinstance(v, (bool, str)) or (isinstance(v, float) and v != int(v)):
+                        raise ValueError(f"n must be an integer in [1, {MAX_N}]")
+                    v = int(v)
                 elif f.name in ("stop_token_ids",):
                     v = tuple(int(x) for x in v)
                 elif f.name == "stop":
@@ -192,6 +202,15 @@ class SamplingParams:
         return cls(**kw)
 
 
+def check_n(llm, params: SamplingParams) -> None:
+    """``params.n`` against the sequence cap of the engine behind ``llm`` (an AsyncLLM or a pool of
+    them), where a front end can see it; the engine checks again at ``add_request``."""
+    eng = getattr(llm, "engine", None)
+    cap = eng.cfg.max_num_seqs if eng is not None else None
+    if cap is not None and params.n > cap:
+        raise ValueError(f"n must be at most max_num_seqs ({cap}), got {params.n}")
+
+
 class SeqStatus(enum.Enum):
     WAITING = 0
     RUNNING = 1
@@ -212,12 +231,18 @@ class Sequence:
     __slots__ = ("seq_id", "request_id", "prompt_ids", "output_ids", "params", "status", "num_computed",
                  "arrival", "first_scheduled", "first_token_time", "finish_time", "finish_reason",
                  "num_preemptions", "eos_token_id", "token_times", "user", "num_cached_tokens",
-                 "cache_salt", "logprobs", "grammar", "spec_state", "spec_drafted", "spec_accepted")
+                 "cache_salt", "logprobs", "grammar", "spec_state", "spec_drafted", "spec_accepted",
+                 "index", "choices", "forked_tokens")
 
     def __init__(self, request_id: str, prompt_ids: List[int], params: SamplingParams, eos_token_id: int = -1,
-                 user=None, cache_salt: Optional[str] = None):
+                 user=None, cache_salt: Optional[str] = None, index: int = 0):
         self.seq_id = next(_ids)
         self.request_id = request_id
+        # parallel sampling: the choice this sequence is of its request, every choice of the request
+        # (None for n = 1), and the prompt tokens whose KV it got from choice 0's by a fork
+        self.index = index
+        self.choices: Optional[List["Sequence"]] = None
+        self.forked_tokens = 0
         self.prompt_ids = list(prompt_ids)
         self.output_ids: List[int] = []
         self.params = params
@@ -262,8 +287,14 @@ class Sequence:
         return self.prompt_ids[start:] + self.output_ids[:end - n]
 
     @property
+    def key(self):
+        """The scheduler's registry key: the request id for choice 0 (so n = 1 is as ever), (id, index) beyond."""
+        return self.request_id if self.index == 0 else (self.request_id, self.index)
+
+    @property
     def seed(self) -> int:
-        return (self.params.seed if self.params.seed is not None else self.seq_id * 2654435761) & 0x7FFFFFFF
+        return (self.params.seed + self.index if self.params.seed is not None
+                else self.seq_id * 2654435761) & 0x7FFFFFFF
 
     def is_finished(self) -> bool:
         return self.status == SeqStatus.FINISHED
@@ -290,6 +321,9 @@ class RequestOutput:
     num_prompt_tokens: int = 0
     num_output_tokens: int = 0
     metrics: Optional[dict] = None
+    # the choice of the request (parallel sampling) this output belongs to; ``finished`` and
+    # ``finish_reason`` refer to that choice.  Keyword-only: the positional order ends with logprobs
+    index: int = dataclasses.field(default=0, kw_only=True)
     # one (logprob, [(id, logprob) x n]) per entry of new_token_ids when the request asked for them
     logprobs: Optional[list] = None
 
@@ -306,6 +340,8 @@ def seq_metrics(s: Sequence) -> dict:
         "ttft_s": ttft, "e2e_s": e2e, "mean_itl_s": itl, "preemptions": s.num_preemptions,
         "cached_prompt_tokens": s.num_cached_tokens,
     }
+    if s.choices is not None:  # a choice of an n > 1 request
+        m["forked_prompt_tokens"] = s.forked_tokens
     if s.spec_drafted is not None:  # an engine with speculative decoding configured
         m["spec_drafted"] = s.spec_drafted
         m["spec_accepted"] = s.spec_accepted

@@ -90,6 +90,9 @@ SIGNATURES = {
     # multi-LoRA shrink / expand (csrc/kernels/lora.hip)
     "pk_lora_shrink": [P, P, I64, P, P, P, I32, I32, I32, I32, I32, P, I32, F32, P],
     "pk_lora_expand": [P, I64, I32, P, P, P, P, P, I32, I32, I32, I32, I32, I32, I32, I32, P],
+    # KV block copy of the prompt fork (csrc/kernels/kv_copy.hip): pointer table, n_tensors, block_bytes,
+    # num_blocks, host (src, dst) pairs, n_pairs, stream
+    "pk_kv_copy_blocks": [P, I32, I64, I32, P, I32, P],
 }
 
 

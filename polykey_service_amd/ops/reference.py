@@ -296,6 +296,23 @@ def rope_and_cache(qkv: torch.Tensor, positions: torch.Tensor, cos_sin: torch.Te
     return q
 
 
+def kv_copy_blocks(kv_caches, pairs) -> None:
+    """Block ``dst`` := block ``src`` in every K and V cache of ``kv_caches`` ([(k, v)] per layer), for
+    every (src, dst) pair, as raw bytes.  ValueError (nothing written) for what pk_kv_copy_blocks
+    refuses: more than 32 pairs, an id outside the cache, src == dst, a dst named twice or also a src."""
+    pairs = [(int(s), int(d)) for s, d in pairs]
+    nb = kv_caches[0][0].shape[0]
+    dsts = [d for _, d in pairs]
+    if (len(pairs) > 32 or any(not 0 <= s < nb or not 0 <= d < nb or s == d for s, d in pairs)
+            or len(set(dsts)) != len(dsts) or set(dsts) & {s for s, _ in pairs}):
+        raise ValueError("kv_copy_blocks: invalid (src, dst) pairs")
+    for kv in kv_caches:
+        for t in kv:
+            raw = t.view(torch.uint8)
+            for s, d in pairs:
+                raw[d].copy_(raw[s])
+
+
 # ------------------------------------------------------------------------- attention
 def gather_kv(k_cache, v_cache, block_table, n_tokens):
     """→ K [n, n_kv, D], V [n, n_kv, D] for one sequence (FP8 caches: the raw bytes, as FP8)."""

@@ -59,6 +59,18 @@ class Metrics:
                                    registry=r)
         self.spec_accepted = Counter("polykey_engine_spec_accepted_tokens_total", "draft tokens accepted by verify "
                                      "steps", registry=r)
+        # parallel sampling (n > 1): requests whose choices took choice 0's prompt KV by a fork, requests
+        # whose choices prefilled it themselves instead, prompt tokens the forked choices did not prefill
+        self.kv_forks = Counter("polykey_engine_kv_forks_total", "n > 1 requests whose choices were forked from "
+                                "choice 0's prompt KV", registry=r)
+        self.kv_fork_fallbacks = Counter("polykey_engine_kv_fork_fallbacks_total", "n > 1 requests with a choice "
+                                         "that prefilled the prompt itself (no free block, fork off, TP / EP)",
+                                         registry=r)
+        self.kv_fork_shared = Counter("polykey_engine_kv_fork_shared_tokens_total", "prompt tokens forked choices "
+                                      "were handed (see ..._kv_fork_undone_tokens_total)", registry=r)
+        self.kv_unforked = Counter("polykey_engine_kv_fork_undone_tokens_total", "forked prompt tokens handed back "
+                                   "before their choice first ran (failed admission, a preemption) and prefilled "
+                                   "after all", registry=r)
         self._last: dict = {}
         self.cached_blocks = Gauge("polykey_engine_prefix_cache_blocks", "KV blocks registered in the prefix cache",
                                    registry=r)
@@ -102,6 +114,10 @@ class Metrics:
         self._advance(self.spec_steps, "spec_steps", getattr(engine, "spec_steps", 0))
         self._advance(self.spec_drafts, "spec_drafts", getattr(engine, "spec_draft_tokens", 0))
         self._advance(self.spec_accepted, "spec_accepted", getattr(engine, "spec_accepted_tokens", 0))
+        self._advance(self.kv_forks, "kv_forks", getattr(engine, "kv_forks", 0))
+        self._advance(self.kv_fork_fallbacks, "kv_fork_fallbacks", getattr(engine, "kv_fork_fallbacks", 0))
+        self._advance(self.kv_fork_shared, "kv_fork_shared", getattr(engine, "kv_fork_shared_tokens", 0))
+        self._advance(self.kv_unforked, "kv_unforked", getattr(sch, "num_unforked_tokens", 0))
         n = 0
         for o in outputs:
             n += len(o.new_token_ids)
