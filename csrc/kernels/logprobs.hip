@@ -14,6 +14,16 @@
 //    total order is unique, so exactly n elements compare >= it.
 //  * a row whose maximum is -inf reports -inf for every logprob (never NaN).
 // Output: 41 32-bit words per row, [logprob | 20 ids | 20 logprobs]; slots n..19 hold -1 / -inf.
+//
+// The same body, instantiated with kPrompt, scores a row against a *given* target (prompt
+// logprobs: the target is the next prompt token) and also reports the target's 1-based rank in
+// the total order, 1 + #{j : x_j > x_t, or x_j == x_t and j < t}.  The rank is counted in pass 2,
+// from the loads the sum of exponentials already makes (a compare on the keys and the index, one
+// extra integer block sum), so a row that asks for no list is still read exactly twice.
+//  * targets[row] < 0 or n_top[row] < 0: nothing read, nothing written.
+//  * targets[row] >= V: logprob -inf, rank 0, the list as usual.
+//  * a row whose maximum is -inf: logprob -inf, the rank by the same formula.
+// Output: 42 words per row, [logprob | rank i32 | 20 ids | 20 logprobs].
 #include "sampler_common.h"
 
 using namespace pk;
@@ -22,7 +32,8 @@ namespace {
 
 constexpr int kThreads = kRowThreads;
 constexpr int kNMax = 20;
-constexpr int kRowWords = 1 + 2 * kNMax;
+template <bool kPrompt>
+constexpr int kHead = kPrompt ? 2 : 1;  // words before the list: logprob (| rank)
 constexpr int kCand = 128;  // candidates the final rank-sort takes (LDS)
 
 struct Smem {
@@ -39,18 +50,38 @@ struct Smem {
 // -0.0 and +0.0 compare equal, so they share a key (ties go by index)
 __device__ __forceinline__ uint32_t vkey(float f) { return okey(f == 0.f ? 0.f : f); }
 
-template <typename T>
+__device__ __forceinline__ int block_sum_int(int v, int* red) {
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  if (lane == 0) red[wid] = v;
+  __syncthreads();
+  int t = lane < kThreads / 64 ? red[lane] : 0;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) t += __shfl_xor(t, o, 64);
+  __syncthreads();
+  return t;
+}
+
+// kPrompt = false: `tokens` are the sampled ids (pk_logprobs); true: the targets (pk_prompt_logprobs).
+template <typename T, bool kPrompt>
 __global__ void __launch_bounds__(kThreads) logprobs_kernel(uint32_t* __restrict__ out, const T* __restrict__ logits,
                                                             int64_t stride, int V, const int* __restrict__ tokens,
                                                             const int* __restrict__ n_top) {
   const int row = blockIdx.x;
   int n = n_top[row];
   if (n < 0) return;  // not requested: nothing read, nothing written
+  int target = 0;
+  if constexpr (kPrompt) {
+    target = tokens[row];
+    if (target < 0) return;  // a row without a target (decode row, last prompt row, entry on record)
+  }
+  constexpr int kH = kHead<kPrompt>;
   __shared__ Smem sm;
   n = min(min(n, kNMax), V);
   const T* x = logits + row * stride;
   const int nv = V / 8;
-  uint32_t* o = out + static_cast<int64_t>(row) * kRowWords;
+  uint32_t* o = out + static_cast<int64_t>(row) * (kH + 2 * kNMax);
 
   // ---- pass 1: max
   float best = -INFINITY;
@@ -70,9 +101,25 @@ __global__ void __launch_bounds__(kThreads) logprobs_kernel(uint32_t* __restrict
   const float xmax = best;
   const bool dead = !(xmax > -INFINITY);  // every entry is -inf
 
-  // ---- pass 2: sum exp(x - max)
+  // ---- pass 2: sum exp(x - max); with kPrompt also the elements ahead of the target in the
+  // total order (a dead row still walks: its rank follows the same formula, its z is unused)
   float z = 0.f;
-  if (!dead) {
+  int ahead = 0;
+  if constexpr (kPrompt) {
+    const bool in = target < V;
+    const uint32_t tkey = in ? vkey(Row<T>::load1(x, target)) : 0u;
+    for (int v = threadIdx.x; v < nv; v += kThreads) {
+      float f[8];
+      Row<T>::load8(x, v, f);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        z += __expf(f[j] - xmax);
+        const uint32_t key = vkey(f[j]);
+        ahead += (in && (key > tkey || (key == tkey && 8 * v + j < target))) ? 1 : 0;
+      }
+    }
+    ahead = block_sum_int(ahead, sm.ired);
+  } else if (!dead) {
     for (int v = threadIdx.x; v < nv; v += kThreads) {
       float f[8];
       Row<T>::load8(x, v, f);
@@ -84,15 +131,16 @@ __global__ void __launch_bounds__(kThreads) logprobs_kernel(uint32_t* __restrict
   const float lse = dead ? -INFINITY : xmax + __logf(z);
 
   if (threadIdx.x == 0) {
-    const int t = tokens[row];
+    const int t = kPrompt ? target : tokens[row];
     float lp = -INFINITY;
     if (!dead && t >= 0 && t < V) lp = Row<T>::load1(x, t) - lse;
     o[0] = __float_as_uint(lp);
+    if constexpr (kPrompt) o[1] = static_cast<uint32_t>(target < V ? ahead + 1 : 0);
   }
   if (n == 0) {
     if (threadIdx.x < kNMax) {
-      o[1 + threadIdx.x] = 0xffffffffu;
-      o[1 + kNMax + threadIdx.x] = __float_as_uint(-INFINITY);
+      o[kH + threadIdx.x] = 0xffffffffu;
+      o[kH + kNMax + threadIdx.x] = __float_as_uint(-INFINITY);
     }
     return;
   }
@@ -204,13 +252,13 @@ __global__ void __launch_bounds__(kThreads) logprobs_kernel(uint32_t* __restrict
       rank += (ck > key || (ck == key && ci < idx)) ? 1 : 0;
     }
     if (rank < n) {
-      o[1 + rank] = idx;
-      o[1 + kNMax + rank] = __float_as_uint(dead ? -INFINITY : from_okey(key) - lse);
+      o[kH + rank] = idx;
+      o[kH + kNMax + rank] = __float_as_uint(dead ? -INFINITY : from_okey(key) - lse);
     }
   }
   if (static_cast<int>(threadIdx.x) >= min(n, nc) && threadIdx.x < kNMax) {
-    o[1 + threadIdx.x] = 0xffffffffu;
-    o[1 + kNMax + threadIdx.x] = __float_as_uint(-INFINITY);
+    o[kH + threadIdx.x] = 0xffffffffu;
+    o[kH + kNMax + threadIdx.x] = __float_as_uint(-INFINITY);
   }
 }
 
@@ -224,15 +272,40 @@ PK_EXPORT int pk_logprobs(void* out, const void* logits, const void* tokens, con
   if (B <= 0) return 0;
   if (V <= 0 || V % 8 || stride % 8 || stride < V) return -1;
   if (dtype == 0) {
-    logprobs_kernel<bf16_t><<<B, kThreads, 0, stream>>>(static_cast<uint32_t*>(out), static_cast<const bf16_t*>(logits),
-                                                        stride, V, static_cast<const int*>(tokens),
-                                                        static_cast<const int*>(n_top));
+    logprobs_kernel<bf16_t, false><<<B, kThreads, 0, stream>>>(static_cast<uint32_t*>(out),
+                                                               static_cast<const bf16_t*>(logits),
+                                                        stride, V,
+                                                               static_cast<const int*>(tokens),
+                                                               static_cast<const int*>(n_top));
   } else if (dtype == 1) {
-    logprobs_kernel<float><<<B, kThreads, 0, stream>>>(static_cast<uint32_t*>(out), static_cast<const float*>(logits),
-                                                       stride, V, static_cast<const int*>(tokens),
-                                                       static_cast<const int*>(n_top));
+    logprobs_kernel<float, false><<<B, kThreads, 0, stream>>>(static_cast<uint32_t*>(out),
+                                                              static_cast<const float*>(logits),
+                                                       stride, V,
+                                                              static_cast<const int*>(tokens),
+                                                              static_cast<const int*>(n_top));
   } else {
     return -1;
+  }
+  return PK_CHECK_LAUNCH();
+}
+
+// out: [R, 42] 32-bit words, row = [logprob f32 | rank i32 | 20 ids i32 | 20 logprobs f32] of
+// targets[r] under logits row r.  targets int[R]: the id to score, < 0 = row not asked
+// (untouched); n_top int[R]: -1 = not asked, 0..20 = length of the top list.  Never captured.
+PK_EXPORT int pk_prompt_logprobs(void* out, const void* logits, const void* targets, const void* n_top, int R, int V,
+                                 int stride, int dtype, hipStream_t stream) {
+  if (V <= 0 || V % 8 || stride % 8 || stride < V || (dtype != 0 && dtype != 1)) return -1;
+  if (R <= 0) return 0;
+  if (dtype == 0) {
+    logprobs_kernel<bf16_t, true><<<R, kThreads, 0, stream>>>(static_cast<uint32_t*>(out),
+                                                              static_cast<const bf16_t*>(logits), stride, V,
+                                                              static_cast<const int*>(targets),
+                                                              static_cast<const int*>(n_top));
+  } else {
+    logprobs_kernel<float, true><<<R, kThreads, 0, stream>>>(static_cast<uint32_t*>(out),
+                                                             static_cast<const float*>(logits), stride, V,
+                                                             static_cast<const int*>(targets),
+                                                             static_cast<const int*>(n_top));
   }
   return PK_CHECK_LAUNCH();
 }

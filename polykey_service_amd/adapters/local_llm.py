@@ -32,6 +32,10 @@ the summary then gains ``choices: [{index, text, finish_reason, token_ids?, logp
 top-level ``text`` / ``finish_reason`` stay those of index 0, ``usage.prompt_tokens`` counts the prompt
 once and ``completion_tokens`` sums the choices.  ``n > 1`` with function tools, without the struct, or
 on ``ExecuteToolStream`` is ``INVALID_ARGUMENT``.
+``prompt_logprobs`` (0..20: every prompt token scored given the tokens before it, from the raw logits)
+needs ``return: "struct"``; the summary then gains ``prompt_logprobs: {token_ids, token_logprobs (first
+null), ranks (first null), top_logprobs: [[{id, logprob}]]}``.  With function tools, without the struct,
+or on ``ExecuteToolStream`` it is ``INVALID_ARGUMENT``.
 """
 from __future__ import annotations
 
@@ -146,6 +150,8 @@ class LLMTool:
             raise ToolError("INVALID_ARGUMENT", "'logprobs' cannot be combined with function tools")
         if sp.n > 1:
             raise ToolError("INVALID_ARGUMENT", "'n' > 1 cannot be combined with function tools")
+        if sp.prompt_logprobs is not None:
+            raise ToolError("INVALID_ARGUMENT", "'prompt_logprobs' cannot be combined with function tools")
         try:
             rounds = tool_rounds(params.get("max_tool_rounds"))
         except ValueError as e:
@@ -178,12 +184,15 @@ class LLMTool:
         t0 = time.monotonic()
         prompt = self._prompt(params)
         sp = self._sampling(params)
+        if sp.prompt_logprobs is not None and params.get("return") != "struct":
+            raise ToolError("INVALID_ARGUMENT", "'prompt_logprobs' needs 'return': 'struct' (a string holds no scores)")
         if sp.n > 1:
             if params.get("return") != "struct":
                 raise ToolError("INVALID_ARGUMENT", "'n' > 1 needs 'return': 'struct' (a string holds one completion)")
             return await self._run_choices(ctx, params, prompt, sp, t0)
         toks: List[int] = []
         lps: Optional[list] = [] if sp.logprobs is not None else None
+        plp: Optional[list] = None
         last = None
         text = ""
         # without stop strings a unary call needs only the final result: a remote engine
@@ -192,6 +201,8 @@ class LLMTool:
             toks.extend(out.new_token_ids)
             if lps is not None:
                 lps.extend(out.logprobs or [])
+            if out.prompt_logprobs is not None:
+                plp = out.prompt_logprobs
             last = out
             if sp.stop:
                 text = self.tok.decode(toks)
@@ -203,8 +214,10 @@ class LLMTool:
             text = self.tok.decode(toks)
         resp = proto.ExecuteToolResponse(status=_status())
         if params.get("return") == "struct":
-            resp.struct_output.update(self._summary(text, len(prompt), toks, last, t0,
-                                                    bool(params.get("return_token_ids")), lps, sp.lora))
+            out = self._summary(text, len(prompt), toks, last, t0, bool(params.get("return_token_ids")), lps, sp.lora)
+            if sp.prompt_logprobs is not None:
+                out["prompt_logprobs"] = lpf.struct_prompt_block(prompt, plp or [None] * len(prompt))
+            resp.struct_output.update(out)
         else:
             resp.string_output = text
         return resp
@@ -233,6 +246,9 @@ class LLMTool:
         n_out = sum(len(t) for t in all_toks)
         out["usage"] = {"prompt_tokens": len(prompt), "completion_tokens": n_out, "total_tokens": len(prompt) + n_out}
         out["choices"] = choices
+        if sp.prompt_logprobs is not None:  # the request's: one prompt, scored once (by choice 0)
+            plp = lasts[0].prompt_logprobs if lasts[0] is not None else None
+            out["prompt_logprobs"] = lpf.struct_prompt_block(prompt, plp or [None] * len(prompt))
         resp = proto.ExecuteToolResponse(status=_status())
         resp.struct_output.update(out)
         return resp
@@ -248,6 +264,9 @@ class LLMTool:
         if sp.n > 1:
             raise ToolError("INVALID_ARGUMENT", "'n' > 1 is not supported on ExecuteToolStream (use ExecuteTool "
                                                 "with 'return': 'struct')")
+        if sp.prompt_logprobs is not None:
+            raise ToolError("INVALID_ARGUMENT", "'prompt_logprobs' is not supported on ExecuteToolStream (use "
+                                                "ExecuteTool with 'return': 'struct')")
         toks: List[int] = []
         lps: Optional[list] = [] if sp.logprobs is not None else None
         last = None

@@ -20,6 +20,15 @@ carry the entries of the tokens that arrived with them (also when the detokenize
 back and the chunk's content is ``""``).  Non-finite values are sent as ``-9999.0``.  Logprobs
 cannot be combined with function tools (400).
 
+Prompt logprobs: ``prompt_logprobs: 0..20`` (the vLLM extension, both endpoints) adds
+``prompt_logprobs: [null, {token_id, token, logprob, rank, top_logprobs: [{token_id, token, logprob}]},
+...]`` to every choice: each prompt token scored given the tokens before it, from the raw logits.
+``echo: true`` on ``/v1/completions`` prepends the decoded prompt to ``text``; with ``logprobs: k`` the
+``logprobs`` block then covers prompt + completion (entry 0 of ``token_logprobs`` / ``top_logprobs`` is
+``null``, ``text_offset`` starts at 0), without ``logprobs`` it costs no GPU work.  ``max_tokens: 0`` is
+accepted only together with ``echo``: one token is generated and dropped (``completion_tokens`` 0,
+``finish_reason`` ``"length"``).  Neither can be streamed or combined with function tools (400).
+
 Penalties: ``frequency_penalty`` / ``presence_penalty`` (-2..2), ``repetition_penalty`` (> 0) and
 ``logit_bias`` ({token id: -100..100}, at most 300 entries) are applied before sampling
 (ops/penalties.py); out-of-range values are a 400.  They may be combined with function tools, and
@@ -133,11 +142,19 @@ def create_app(router):
         return {"object": "list", "data": data}
 
     async def _run(body: Dict[str, Any], chat: bool):
+        drop = False  # echo with max_tokens 0: the one generated token is not reported
         try:
             llm, model = _llm(router, body.get("model"))
+            n_pl, echo = lpf.parse_prompt_logprobs(body, chat)
+            if echo and body.get("max_tokens") == 0 and not isinstance(body["max_tokens"], bool):
+                body, drop = {**body, "max_tokens": 1}, True
             sp = _params(body, chat)
+            sp.prompt_logprobs = n_pl
+            n_pl = body.get("prompt_logprobs")  # the length of the lists the client asked for itself
             sp.lora = _lora(router, body.get("model"))
             check_n(llm, sp)
+            if body.get("stream") and (echo or sp.prompt_logprobs is not None):
+                raise ValueError("'echo' / 'prompt_logprobs' cannot be combined with 'stream'")
         except ToolError as e:
             return err(404 if e.code == "NOT_FOUND" else 503, e.message)
         except (ValueError, TypeError) as e:
@@ -156,6 +173,8 @@ def create_app(router):
                     return err(400, "'logprobs' cannot be combined with function tools")
                 if sp.n > 1:
                     return err(400, "'n' > 1 cannot be combined with function tools")
+                if sp.prompt_logprobs is not None:
+                    return err(400, "'prompt_logprobs' cannot be combined with function tools")
                 return await _run_tools(body, llm, model, msgs, sp, tools, choice)
             prompt_ids = tok.encode(tok.apply_chat_template(msgs))
         else:
@@ -238,19 +257,30 @@ def create_app(router):
             toks, last = await llm.generate_all(prompt_ids, sp, request_id=rid)
             all_toks, lasts = [toks], [last]
         choices = []
+        plp = lasts[0].prompt_logprobs if lasts[0] is not None else None  # the request's, on choice 0's output
+        if drop:
+            all_toks = [[] for _ in all_toks]
         for i, (toks, last) in enumerate(zip(all_toks, lasts)):
             text = tok.decode(toks)
             if sp.stop:
                 cuts = [text.find(s) for s in sp.stop if text.find(s) >= 0]
                 if cuts:
                     text = text[:min(cuts)]
-            choice = ({"index": i, "message": {"role": "assistant", "content": text},
-                       "finish_reason": last.finish_reason if last else None} if chat
-                      else {"index": i, "text": text, "finish_reason": last.finish_reason if last else None})
+            if echo:
+                text = tok.decode(prompt_ids) + text
+            reason = "length" if drop else (last.finish_reason if last else None)
+            choice = ({"index": i, "message": {"role": "assistant", "content": text}, "finish_reason": reason} if chat
+                      else {"index": i, "text": text, "finish_reason": reason})
             if sp.logprobs is not None:
                 entries = (last.logprobs if last else None) or []
-                choice["logprobs"] = ({"content": lpf.chat_content(tok, toks, entries)} if chat
-                                      else lpf.completion_block(tok, toks, entries))
+                if echo:
+                    choice["logprobs"] = lpf.echo_block(tok, prompt_ids, plp or [None] * len(prompt_ids), toks, entries,
+                                                        sp.logprobs)
+                else:
+                    choice["logprobs"] = ({"content": lpf.chat_content(tok, toks, entries)} if chat
+                                          else lpf.completion_block(tok, toks, entries))
+            if n_pl is not None:
+                choice["prompt_logprobs"] = lpf.prompt_list(tok, prompt_ids, plp or [None] * len(prompt_ids), n_pl)
             choices.append(choice)
         return {"id": rid, "object": obj, "created": created, "model": model, "choices": choices,
                 "usage": _usage(len(prompt_ids), sum(len(t) for t in all_toks), lasts[0].metrics if lasts[0] else None)}

@@ -171,7 +171,8 @@ class AsyncLLM:
                     item = RequestOutput(item.request_id, item.new_token_ids + nxt.new_token_ids, nxt.finished,
                                          nxt.finish_reason, nxt.num_prompt_tokens, nxt.num_output_tokens,
                                          nxt.metrics, index=nxt.index,
-                                         logprobs=None if item.logprobs is None else item.logprobs + (nxt.logprobs or []))
+                                         logprobs=None if item.logprobs is None else item.logprobs + (nxt.logprobs or []),
+                                         prompt_logprobs=item.prompt_logprobs)
                 if isinstance(item, BaseException):
                     finished = True
                     raise item
@@ -192,17 +193,21 @@ class AsyncLLM:
     async def generate_all(self, prompt_ids: List[int], params: SamplingParams,
                            request_id: Optional[str] = None) -> Tuple[List[int], RequestOutput]:
         """→ (all token ids, the last output).  When the request asked for logprobs the returned
-        output's ``logprobs`` holds the entries of every token, not of the last chunk only."""
+        output's ``logprobs`` holds the entries of every token, not of the last chunk only, and its
+        ``prompt_logprobs`` the request's prompt logprobs (delivered with the first token)."""
         toks: List[int] = []
         lps: Optional[list] = None
+        plp: Optional[list] = None
         last = None
         async for out in self.generate(prompt_ids, params, request_id):
             toks.extend(out.new_token_ids)
             if out.logprobs is not None:
                 lps = (lps or []) + out.logprobs
+            if out.prompt_logprobs is not None:
+                plp = out.prompt_logprobs
             last = out
-        if last is not None and lps is not None:
-            last = dataclasses.replace(last, logprobs=lps)
+        if last is not None and (lps is not None or plp is not None):
+            last = dataclasses.replace(last, logprobs=lps, prompt_logprobs=plp)
         return toks, last
 
     async def generate_choices(self, prompt_ids: List[int], params: SamplingParams,
@@ -410,17 +415,22 @@ class AsyncLLM:
 
 
 async def collect_choices(stream, n: int) -> Tuple[List[List[int]], List[RequestOutput]]:
-    """Drain a request's output stream into per-index token lists and last outputs."""
+    """Drain a request's output stream into per-index token lists and last outputs (the request's
+    prompt logprobs, when asked for, on index 0's)."""
     toks: List[List[int]] = [[] for _ in range(n)]
     lps: List[Optional[list]] = [None] * n
+    plp: List[Optional[list]] = [None] * n
     last: List[Optional[RequestOutput]] = [None] * n
     async for out in stream:
         i = out.index
         toks[i].extend(out.new_token_ids)
         if out.logprobs is not None:
             lps[i] = (lps[i] or []) + out.logprobs
+        if out.prompt_logprobs is not None:
+            plp[i] = out.prompt_logprobs
         last[i] = out
-    return toks, [o if o is None or lps[i] is None else dataclasses.replace(o, logprobs=lps[i])
+    return toks, [o if o is None or (lps[i] is None and plp[i] is None)
+                  else dataclasses.replace(o, logprobs=lps[i], prompt_logprobs=plp[i])
                   for i, o in enumerate(last)]
 
 

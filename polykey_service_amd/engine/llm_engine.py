@@ -262,6 +262,7 @@ class LLMEngine:
         # runs (Scheduler._unmatch) is counted by the scheduler's num_unforked / num_unforked_tokens
         self.kv_fork = cfg.kv_fork and self.st.tp_size == 1 and self.st.ep_size == 1 and not self.lockstep
         self.kv_forks = self.kv_fork_fallbacks = self.kv_fork_shared_tokens = 0
+        self.prompt_logprob_tokens = 0  # prompt-logprob entries computed (polykey_engine_prompt_logprob_tokens_total)
         if cfg.speculative:
             self.spec_k = cfg.num_speculative_tokens
             self.proposer = spec.NgramProposer(cfg.ngram_max, cfg.ngram_min)
@@ -346,6 +347,12 @@ class LLMEngine:
         if params.lora is not None and params.lora not in self.lora_names:
             raise ValueError(f"unknown LoRA adapter {params.lora!r}: this engine serves "
                              f"{', '.join(self.lora_names) if self.lora_names else 'no adapters'}")
+        if params.prompt_logprobs is not None:
+            # the workers of a TP / EP group have no step message naming the rows (out of scope)
+            if self.st.tp_size > 1:
+                raise ValueError(f"prompt_logprobs does not support tp={self.st.tp_size}")
+            if self.st.ep_size > 1 or self.lockstep:
+                raise ValueError(f"prompt_logprobs does not support ep={self.st.ep_size} / DP attention")
         if params.n > self.cfg.max_num_seqs:
             raise ValueError(f"n must be at most max_num_seqs ({self.cfg.max_num_seqs}), got {params.n}")
         g = self._grammar(params)
@@ -388,7 +395,10 @@ class LLMEngine:
         return g
 
     def abort(self, request_id: str) -> Optional[Sequence]:
-        return self.scheduler.abort(request_id)
+        seq = self.scheduler.abort(request_id)
+        if seq is not None and seq.prompt_logprobs is not None:
+            seq.prompt_logprobs, seq.prompt_lp_missing = None, 0  # the entries gathered so far
+        return seq
 
     def has_unfinished(self) -> bool:
         return self.scheduler.has_work() or self._inflight is not None
@@ -587,6 +597,12 @@ class LLMEngine:
         toks = self.runner.fetch(handle)
         # packed logprob rows in sampling order, fetched only when a sequence of the step asked
         lp_rows = self.runner.fetch_logprobs(handle) if len(handle) > 4 and handle[4] is not None else None
+        for s, i, entry in self.runner.fetch_prompt_logprobs(handle):
+            # (an entry is computed once: prompt_targets skips those on record, also in a recompute)
+            if s.prompt_logprobs is not None and s.prompt_logprobs[i] is None:
+                s.prompt_logprobs[i] = entry
+                s.prompt_lp_missing -= 1
+                self.prompt_logprob_tokens += 1
         now = time.monotonic()
         for s, n in batch.prefills:
             s.num_computed += n
@@ -649,10 +665,17 @@ class LLMEngine:
 
     @staticmethod
     def _outputs(done) -> List[RequestOutput]:
-        return [RequestOutput(s.request_id, toks, reason is not None, reason.value if reason else None,
-                              len(s.prompt_ids), len(s.output_ids), seq_metrics(s) if reason else None,
-                              index=s.index, logprobs=s.logprobs[-len(toks):] if s.logprobs is not None else None)
-                for s, toks, reason in done]
+        outs = []
+        for s, toks, reason in done:
+            out = RequestOutput(s.request_id, toks, reason is not None, reason.value if reason else None,
+                                len(s.prompt_ids), len(s.output_ids), seq_metrics(s) if reason else None,
+                                index=s.index, logprobs=s.logprobs[-len(toks):] if s.logprobs is not None else None)
+            if s.prompt_logprobs is not None and not s.prompt_lp_delivered:
+                # once, with the first generated token (the prompt is computed: every entry exists)
+                out.prompt_logprobs = list(s.prompt_logprobs)
+                s.prompt_lp_delivered = True
+            outs.append(out)
+        return outs
 
     def generate(self, prompts: List[List[int]], params: SamplingParams) -> List[List[int]]:
         seqs = [self.add_request(p, dataclasses.replace(params)) for p in prompts]

@@ -24,6 +24,7 @@ a measured activation peak — at 288 GB per MI355X an 8B model gets ~1.9 M cach
 from __future__ import annotations
 
 import dataclasses
+import logging
 import math
 import os
 import threading
@@ -65,6 +66,31 @@ class RunnerConfig:
 # tools/bench_attn.py).  Step inputs are staged by a kernel reading pinned memory instead of an
 # SDMA copy.  Each decode bucket has a second graph for steps whose contexts all fit one attention
 # partition (one workgroup per (seq, kv head), no merge kernel).
+
+
+# Prompt logprobs (SamplingParams.prompt_logprobs): the LM head runs over the asked prompt rows of a
+# prefill step in chunks of at most this many rows, so the logits it materialises stay bounded
+# (256 x V_padded x 2 bytes: 66 MB at V = 128,256) however long the prompt chunk is.
+PROMPT_LP_CHUNK_ROWS = 256
+
+
+def prompt_targets(chunks) -> List[int]:
+    """The prompt-logprob target of every row of a step.  ``chunks``: the step's scheduled
+    ``(seq, start, length)`` in row order (a decode row is a chunk of length 1).  The row at
+    position ``p`` of a sequence that asks gets ``prompt_ids[p + 1]`` -- the token its logits
+    predict, taken from the prompt itself, so the last row of a non-final chunk has its target
+    too -- when ``p + 1`` is still inside the prompt and entry ``p + 1`` is not on record yet;
+    every other row (decode rows, the prompt's last row, rows of sequences that do not ask, rows of
+    a recompute whose entries exist) gets -1."""
+    out: List[int] = []
+    for seq, start, length in chunks:
+        rec = seq.prompt_logprobs
+        if rec is None or not seq.prompt_lp_missing:
+            out += [-1] * length
+            continue
+        ids, P = seq.prompt_ids, len(seq.prompt_ids)
+        out += [ids[p + 1] if p + 1 < P and rec[p + 1] is None else -1 for p in range(start, start + length)]
+    return out
 
 
 class _Layout:
@@ -156,6 +182,25 @@ class ModelRunner:
         self._lp_hosts = [torch.zeros((n_samp, sampler_ops.LOGPROB_WORDS), dtype=torch.int32,
                                       pin_memory=pin) for _ in range(2)]
         self._tok_i = 0
+        # prompt logprobs: device records for the asked rows of one step, and their inputs (row
+        # index, target id, list length per asked row) in a small pinned buffer of their own, copied
+        # only in steps that have such a row -- the staging layout above and the step-channel frame
+        # are what they were.  Both are double-buffered like the sampled ids.  Their bytes are reserved
+        # here, before the KV cache is sized (activation_reserve_bytes); the buffers themselves are made
+        # by the first step that needs them (_prompt_lp_buffers), so an engine that never scores a
+        # prompt makes the allocations of an engine without the feature, one for one.
+        W = sampler_ops.PROMPT_LOGPROB_WORDS
+        self.plp_dev = self.plp_in_dev = self._plp_in_hosts = self._plp_hosts = None
+        self._plp_events = [None, None]
+        self._plp_i = 0
+        self._plp = None      # launch -> _run: (asked rows, owners) of the step being launched
+        self._plp_out = None  # _run -> launch: (host records, rows, owners, event)
+        # (bytes of one chunk's logits -- reserved before the KV cache is sized -- , bytes of records)
+        self.prompt_lp_bytes = (PROMPT_LP_CHUNK_ROWS * self.mcfg.vocab_size * model.dtype.itemsize,
+                                (self.max_step_tokens * W + 3 * self.max_step_tokens) * 4)
+        logging.getLogger(__name__).info(
+            "prompt logprobs: %d bytes of logits per %d-row LM-head chunk, %d bytes of records (%d rows x %d words)",
+            self.prompt_lp_bytes[0], PROMPT_LP_CHUNK_ROWS, self.prompt_lp_bytes[1], self.max_step_tokens, W)
         # sampling penalties / logit_bias (ops/penalties.py): device-resident token history, one
         # slot per penalised sequence, allocated before the KV cache is sized.  A sequence gets
         # its slot the first time it samples (launch) and loses it when the scheduler frees its
@@ -199,7 +244,7 @@ class ModelRunner:
         self.part_o, self.part_ml = attn_ops.decode_workspace(cfg.max_num_seqs, a0.nq, self.max_blocks, self.bs, device,
                                                               kv_heads=a0.nkv)
         self.stats = {"steps": 0, "graph_steps": 0, "short_graph_steps": 0, "tokens": 0, "seed_msgs": 0,
-                      "lora_steps": 0, "lora_graph_steps": 0}
+                      "lora_steps": 0, "lora_graph_steps": 0, "prompt_lp_rows": 0, "prompt_lp_steps": 0}
         # verify steps of speculative decoding: graphs per sequence-count bucket (captured only when
         # configured) and partition slabs for verify_max_seqs x spec_qr rows
         self.verify_graphs: Dict[int, torch.cuda.CUDAGraph] = {}
@@ -300,7 +345,8 @@ class ModelRunner:
         tp = self.model.st.tp_size
         per_tok = 2 * (m.hidden_size * 4 + (m.q_size + 2 * m.kv_size) // tp + 3 * m.intermediate_size // tp)
         logits = self.cfg.max_num_seqs * m.vocab_size * 4 * 2
-        return int(T * per_tok * 1.5 + logits + (1 << 30))
+        # (+ one LM-head chunk of prompt-logprob logits and the record / target buffers, made on first use)
+        return int(T * per_tok * 1.5 + logits + sum(self.prompt_lp_bytes) + (1 << 30))
 
     # ------------------------------------------------------------------ inputs
     def _pack(self, batch: ScheduledBatch, sampling: List[Sequence]):
@@ -734,8 +780,13 @@ class ModelRunner:
         lora = self._step_lora if self.lora is not None else 0
         h["header"][:11] = (self.MODE_RUN, T, n, nd, ns, max_q, g, short, 0, lora, 0)
         self._publish(max(n, g))
+        if batch.prefills and any(s.prompt_lp_missing for s, _ in batch.prefills):
+            self._stage_prompt_lp(batch)
         toks = self._run(T, n, nd, ns, max_q, g, short, lora)
-        return self._handle(toks, ns, want_lp)
+        handle = self._handle(toks, ns, want_lp)
+        if self._plp_out is not None:  # a sixth element, only on steps with prompt-logprob rows
+            handle, self._plp_out = handle + (self._plp_out,), None
+        return handle
 
     def _short(self, g: int, nd: int) -> int:
         """1 when every decode context fits one attention partition: the step replays bucket
@@ -772,6 +823,82 @@ class ModelRunner:
         if lp is None or ns == 0:
             return None
         return lp[:ns].numpy().copy()
+
+    # ------------------------------------------------------------- prompt logprobs
+    def _prompt_lp_buffers(self) -> None:
+        """First step with a prompt-logprob row: the device records and targets and their pinned twins
+        (bytes reserved at start-up, activation_reserve_bytes).  Eager steps only: never under capture."""
+        W, n, pin = sampler_ops.PROMPT_LOGPROB_WORDS, self.max_step_tokens, self.device.type == "cuda"
+        self.plp_dev = torch.zeros((n, W), dtype=torch.int32, device=self.device)
+        self.plp_in_dev = torch.zeros(3 * n, dtype=torch.int32, device=self.device)
+        self._plp_in_hosts = [torch.zeros(3 * n, dtype=torch.int32, pin_memory=pin) for _ in range(2)]
+        self._plp_hosts = [torch.zeros((n, W), dtype=torch.int32, pin_memory=pin) for _ in range(2)]
+
+    def _stage_prompt_lp(self, batch: ScheduledBatch) -> None:
+        """A step with a sequence that still misses prompt-logprob entries: the asked rows, their
+        targets and list lengths go to the device through their own pinned buffer (``_run`` scores
+        them after the forward).  Leaves ``_plp`` None when no row of the step has a target."""
+        chunks = [(s, s.num_computed, 1) for s in batch.decodes] + [(s, s.num_computed, c) for s, c in batch.prefills]
+        targets = prompt_targets(chunks)
+        rows, tgt, ntop, owners = [], [], [], []
+        r = 0
+        for s, start, length in chunks:
+            for p in range(start, start + length):
+                if targets[r] >= 0:
+                    rows.append(r)
+                    tgt.append(targets[r])
+                    ntop.append(s.params.prompt_logprobs)
+                    owners.append((s, p + 1))
+                r += 1
+        R = len(rows)
+        if not R:
+            return
+        if self.plp_dev is None:
+            self._prompt_lp_buffers()
+        self._plp_i ^= 1
+        ev = self._plp_events[self._plp_i]
+        if ev is not None:
+            ev.synchronize()  # the buffers' last use (two such steps back) is over
+        # [rows | targets | list lengths], packed: one contiguous copy of 3 R words from pinned memory
+        hin = self._plp_in_hosts[self._plp_i]
+        hin[:3 * R] = torch.tensor(rows + tgt + ntop, dtype=torch.int32)
+        self.plp_in_dev[:3 * R].copy_(hin[:3 * R], non_blocking=True)
+        self._plp = (R, owners)
+
+    def _score_prompt_rows(self, hidden: torch.Tensor) -> None:
+        """After the forward of a step staged by :meth:`_stage_prompt_lp`: LM head over the asked
+        rows in chunks of PROMPT_LP_CHUNK_ROWS, each scored against its target by the kernel, then
+        one async copy of the records to pinned memory behind an event."""
+        (R, owners), self._plp = self._plp, None
+        rows, tgt, ntop = self.plp_in_dev[:R], self.plp_in_dev[R:2 * R], self.plp_in_dev[2 * R:3 * R]
+        for c0 in range(0, R, PROMPT_LP_CHUNK_ROWS):
+            c1 = min(R, c0 + PROMPT_LP_CHUNK_ROWS)
+            logits = self.model.compute_logits(hidden.index_select(0, rows[c0:c1].long()))
+            sampler_ops.prompt_logprobs(logits, tgt[c0:c1], ntop[c0:c1], self.plp_dev[c0:c1])
+        self.stats["prompt_lp_rows"] += R
+        self.stats["prompt_lp_steps"] += 1
+        if self.device.type != "cuda":
+            self._plp_out = (self.plp_dev[:R].clone(), R, owners, None)
+            return
+        host = self._plp_hosts[self._plp_i]
+        host[:R].copy_(self.plp_dev[:R], non_blocking=True)
+        ev = self._plp_events[self._plp_i]
+        if ev is None:
+            ev = self._plp_events[self._plp_i] = torch.cuda.Event()
+        ev.record(torch.cuda.current_stream(self.device))
+        self._plp_out = (host, R, owners, ev)
+
+    def fetch_prompt_logprobs(self, handle):
+        """The prompt-logprob entries a step computed: ``[(seq, entry index, (logprob, rank, top
+        list))]``, empty for a step without such rows.  Waits for the step's records only."""
+        if len(handle) < 6:
+            return []
+        host, R, owners, ev = handle[5]
+        if ev is not None:
+            ev.synchronize()
+        rec = host[:R].numpy()
+        return [(s, i, sampler_ops.prompt_logprob_entry(rec[j], s.params.prompt_logprobs))
+                for j, (s, i) in enumerate(owners)]
 
     def fetch(self, handle) -> List[int]:
         toks, ns, ev = handle[:3]
@@ -1035,6 +1162,8 @@ class ModelRunner:
             return out
         md = self._metadata(nd, n, T, max_q, bool(short))
         hidden = self.model(d["input_ids"][:T], d["positions"][:T], md, self.kv_caches)
+        if self._plp is not None:
+            self._score_prompt_rows(hidden)
         if ns == 0:
             return None
         rows = hidden if ns == T else hidden.index_select(0, d["sample_idx"][:ns].long())

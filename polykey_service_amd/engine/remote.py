@@ -13,6 +13,9 @@ Wire format: 4-byte little-endian length + a msgpack map per frame.
                                                    (, choice index when it is not 0)], ...]}
 A request with n > 1 choices (parallel sampling) carries "n" in its params and its items carry the choice
 index as a tenth element when it is not 0; frames of n = 1 requests are byte for byte what they were.
+A request with prompt logprobs carries "prompt_logprobs" in its params, and the item of choice 0 that
+reports its first token carries the list as an eleventh element (after an explicit index 0): entries
+null or [logprob, rank, [[id, logprob], ...]]; frames of requests that do not ask stay what they were.
 One "out" frame carries every request's news of one engine step (written by the engine thread
 itself, no event loop in between); a request submitted with ``final`` (unary RPCs without stop
 strings) is reported once, with all its tokens, when it finishes.
@@ -66,6 +69,8 @@ def _params_dict(p: SamplingParams) -> dict:
     d["logit_bias"] = [[int(t), float(b)] for t, b in d["logit_bias"]]  # pairs: msgpack refuses integer map keys
     if d["n"] == 1:
         del d["n"]  # an n = 1 frame stays what it was
+    if p.prompt_logprobs is not None:  # (no dataclass field: a frame that does not ask stays what it was)
+        d["prompt_logprobs"] = p.prompt_logprobs
     return d
 
 
@@ -90,6 +95,7 @@ class EngineServer:
         self._owner: Dict[str, int] = {}   # rid -> connection that submitted it
         self._final: Dict[str, List] = {}  # rid -> tokens so far (final-only requests)
         self._final_lp: Dict[str, List] = {}  # rid -> their logprob entries so far (when requested)
+        self._final_plp: Dict[str, List] = {}  # rid -> its prompt logprobs, held for the final frame
         # n > 1 requests: choices still running; their choices i > 0 accumulate under (rid, i)
         self._left: Dict[str, int] = {}
 
@@ -112,14 +118,19 @@ class EngineServer:
                 if acc is None and o.index and rid in self._final:
                     acc = self._final[key] = []
                 lps = o.logprobs
+                plp = o.prompt_logprobs
                 if acc is not None:
                     acc.extend(o.new_token_ids)
+                    if plp is not None:
+                        self._final_plp[rid] = plp
                     if lps is not None:
                         self._final_lp.setdefault(key, []).extend(lps)
                     if not o.finished:
                         continue
                     ids = acc
                     lps = self._final_lp.pop(key, None)
+                    if not o.index:
+                        plp = self._final_plp.pop(rid, None)
                     if o.index:
                         del self._final[key]
                 else:
@@ -134,6 +145,8 @@ class EngineServer:
                         o.metrics, None, None if lps is None else [[lp, [list(t) for t in top]] for lp, top in lps]]
                 if o.index:
                     item.append(o.index)
+                elif plp is not None:
+                    item += [0, [None if e is None else [e[0], e[1], [list(t) for t in e[2]]] for e in plp]]
                 per.setdefault(cid, []).append(item)
             conns = {cid: self._conns.get(cid) for cid in per}
         for cid, out in per.items():
@@ -153,6 +166,7 @@ class EngineServer:
                     del d[key]
         self._final.pop(rid, None)
         self._final_lp.pop(rid, None)
+        self._final_plp.pop(rid, None)
         self._owner.pop(rid, None)
 
     def _accept(self) -> socket.socket:
@@ -275,12 +289,17 @@ class RemoteEngine:
                             continue
                         lps = rest[0] if rest else None
                         index = rest[1] if len(rest) > 1 else 0
+                        plp = rest[2] if len(rest) > 2 else None
                         if lps is not None:
                             lps = [(float(lp), [(int(i), float(v)) for i, v in top]) for lp, top in lps]
+                        if plp is not None:
+                            plp = [None if e is None else (float(e[0]), int(e[1]), [(int(i), float(v)) for i, v in e[2]])
+                                   for e in plp]
                         if err:  # ("invalid": the engine refused the request itself)
                             item = ValueError(err) if reason == "invalid" else RuntimeError(err)
                         else:
-                            item = RequestOutput(rid, ids, fin, reason, npr, nout, metrics, index=index, logprobs=lps)
+                            item = RequestOutput(rid, ids, fin, reason, npr, nout, metrics, index=index, logprobs=lps,
+                                                 prompt_logprobs=plp)
                         by_loop.setdefault(ent[0], []).append((ent[1], item))
                 for loop, batch in by_loop.items():
                     try:

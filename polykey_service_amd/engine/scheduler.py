@@ -223,6 +223,11 @@ class Scheduler:
         toks = np.asarray(seq.token_slice(0, seq.num_tokens), dtype=np.int32)
         h = self.bm.prefix_hashes(toks, salt=_salt(seq.cache_salt, getattr(seq.params, "lora", None)))
         self._hashes[seq.seq_id] = (h, toks)
+        if seq.prompt_lp_missing:
+            # prompt logprobs still to compute: a cached row is never computed, so it would have no
+            # entry -- the sequence matches nothing (num_cached_tokens stays 0) but commits its blocks
+            # for others; once every entry is on record (re-admission after a preemption) it matches
+            return
         usable = max(0, (seq.num_tokens - 2) // bs)  # >= 2 tokens left: the step still samples
         got = self.bm.match_prefix(seq.seq_id, h, toks, min(usable, len(h)))
         seq.num_computed = got * bs

@@ -67,6 +67,16 @@ class SamplingParams:
     # parallel sampling: the request yields n choices, index 0 .. n-1, each an ordinary sequence with
     # these parameters (choice i samples with seed + i); 1 .. MAX_N and at most the engine's max_num_seqs
     n: int = 1
+    # log-probabilities of the *prompt* tokens (teacher forcing): None = off, 0 = each prompt token's
+    # logprob and rank, 1..20 = plus that many top alternatives; from the raw logits of the row
+    # before the token (ops/sampler.py prompt_logprobs).  Only choice 0 of an n > 1 request computes.
+    # An init-only variable kept as a plain attribute, not a dataclass field: ``dataclasses.fields`` /
+    # ``asdict`` -- and with them the remote-engine frame of a request that does not ask -- are what
+    # they were; ``dataclasses.replace`` carries it, ``from_dict`` and the wire name it explicitly
+    prompt_logprobs: dataclasses.InitVar[Optional[int]] = None
+
+    def __post_init__(self, prompt_logprobs=None):
+        self.prompt_logprobs = prompt_logprobs
 
     @property
     def has_penalties(self) -> bool:
@@ -93,6 +103,9 @@ class SamplingParams:
         if self.logprobs is not None and (isinstance(self.logprobs, bool) or not isinstance(self.logprobs, int)
                                           or not 0 <= self.logprobs <= MAX_LOGPROBS):
             raise ValueError(f"logprobs must be an integer in [0, {MAX_LOGPROBS}]")
+        pl = self.prompt_logprobs
+        if pl is not None and (isinstance(pl, bool) or not isinstance(pl, int) or not 0 <= pl <= MAX_LOGPROBS):
+            raise ValueError(f"prompt_logprobs must be an integer in [0, {MAX_LOGPROBS}]")
         for name in ("frequency_penalty", "presence_penalty"):
             v = getattr(self, name)
             if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v) or not -2 <= v <= 2:
@@ -199,6 +212,11 @@ class SamplingParams:
                         raise ValueError(f"logprobs must be an integer in [0, {MAX_LOGPROBS}]")
                     v = int(v)
                 kw[f.name] = v
+        v = d.get("prompt_logprobs")
+        if v is not None:
+            if isinstance(v, (bool, str)) or (isinstance(v, float) and v != int(v)):
+                raise ValueError(f"prompt_logprobs must be an integer in [0, {MAX_LOGPROBS}]")
+            kw["prompt_logprobs"] = int(v)
         return cls(**kw)
 
 
@@ -232,7 +250,8 @@ class Sequence:
                  "arrival", "first_scheduled", "first_token_time", "finish_time", "finish_reason",
                  "num_preemptions", "eos_token_id", "token_times", "user", "num_cached_tokens",
                  "cache_salt", "logprobs", "grammar", "spec_state", "spec_drafted", "spec_accepted",
-                 "index", "choices", "forked_tokens")
+                 "index", "choices", "forked_tokens", "prompt_logprobs", "prompt_lp_missing",
+                 "prompt_lp_delivered")
 
     def __init__(self, request_id: str, prompt_ids: List[int], params: SamplingParams, eos_token_id: int = -1,
                  user=None, cache_salt: Optional[str] = None, index: int = 0):
@@ -259,6 +278,13 @@ class Sequence:
         self.token_times: List[float] = []
         # one (logprob, [(id, logprob) x n]) per output token; None unless params.logprobs is set
         self.logprobs: Optional[list] = [] if getattr(params, "logprobs", None) is not None else None
+        # prompt logprobs (choice 0 only): entry i = (logprob, rank, [(id, logprob) x n]) of prompt_ids[i]
+        # given prompt_ids[:i], entry 0 None; entries fill in as prefill chunks complete and survive a
+        # preemption.  ``prompt_lp_missing`` counts the entries still to compute (0: not asking)
+        ask = getattr(params, "prompt_logprobs", None) is not None and index == 0
+        self.prompt_logprobs: Optional[list] = [None] * len(self.prompt_ids) if ask else None
+        self.prompt_lp_missing = len(self.prompt_ids) - 1 if ask else 0
+        self.prompt_lp_delivered = False
         self.grammar = None  # the request's compiled constraint (engine/grammar.py), set by add_request
         # speculative decoding: the proposer's per-sequence state, and draft tokens proposed / accepted
         # (None on an engine without speculation: seq_metrics then reports neither)
@@ -324,6 +350,10 @@ class RequestOutput:
     # the choice of the request (parallel sampling) this output belongs to; ``finished`` and
     # ``finish_reason`` refer to that choice.  Keyword-only: the positional order ends with logprobs
     index: int = dataclasses.field(default=0, kw_only=True)
+    # the request's prompt logprobs (SamplingParams.prompt_logprobs): one entry per prompt token, the
+    # first None, the others (logprob, rank, [(id, logprob) x n]); set once, on the index-0 output
+    # that carries the first generated token.  Keyword-only too
+    prompt_logprobs: Optional[list] = dataclasses.field(default=None, kw_only=True)
     # one (logprob, [(id, logprob) x n]) per entry of new_token_ids when the request asked for them
     logprobs: Optional[list] = None
 

@@ -50,6 +50,8 @@ SIGNATURES = {
     "pk_sample": [P, P, P, P, P, P, P, P, P, I32, I32, I32, I32, P],
     "pk_sample_alt": [P, P, P, P, P, P, P, P, I32, I32, I32, I32, P, I64, P, I32, P],
     "pk_logprobs": [P, P, P, P, I32, I32, I32, I32, P],
+    # out, logits, targets, n_top, R, V, stride, dtype, stream (csrc/kernels/logprobs.hip, the kPrompt form)
+    "pk_prompt_logprobs": [P, P, P, P, I32, I32, I32, I32, P],
     "pk_penalty_seed": [P, I64, P, P, P, P, I32, P, I32, I32, I32, P],
     "pk_penalty_apply": [P, I64, P, I64, I32, I32, I32, P, I64, P, P, P, P, P, P, P, I32, P],
     "pk_penalty_update": [P, I64, P, P, I32, I32, I32, P],

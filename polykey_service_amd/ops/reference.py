@@ -530,6 +530,50 @@ def logprobs(logits: torch.Tensor, tokens, n_top, out: torch.Tensor = None) -> t
     return out
 
 
+def prompt_logprobs(logits: torch.Tensor, targets, n_top, out: torch.Tensor = None) -> torch.Tensor:
+    """Log-probability, rank and top-n list of a *given* target per row, from the raw logits, in
+    float64 (the CPU engine's prompt logprobs).
+
+    As :func:`logprobs`, plus the target's 1-based rank in the total order (value descending, id
+    ascending, -0.0 == +0.0): ``1 + #{j : x_j > x_t, or x_j == x_t and j < t}``, counted on the
+    exact values.  Output: packed int32 ``[R, 42]`` rows ``[logprob | rank | 20 ids | 20 logprobs]``;
+    rows with ``targets < 0`` or ``n_top < 0`` are left as they are; ``targets >= V`` reports
+    logprob -inf and rank 0; a row whose maximum is -inf reports -inf and the rank by the formula."""
+    R, V = logits.shape
+    nmax = 20
+    if out is None:
+        out = torch.zeros((R, 2 + 2 * nmax), dtype=torch.int32)
+    if all(int(n_top[r]) < 0 or int(targets[r]) < 0 for r in range(R)):
+        return out
+    x = logits.detach().cpu().double()
+    fl = out.view(torch.float32)
+    ninf = float("-inf")
+    for r in range(R):
+        n, t = int(n_top[r]), int(targets[r])
+        if n < 0 or t < 0:
+            continue
+        n = min(n, nmax, V)
+        row = x[r]
+        m = float(row.max())
+        dead = m == ninf
+        lse = ninf if dead else m + float(torch.log(torch.exp(row - m).sum()))
+        if t < V:
+            xt = row[t]
+            fl[r, 0] = ninf if dead else float(xt) - lse
+            out[r, 1] = 1 + int((row > xt).sum()) + int((row[:t] == xt).sum())
+        else:
+            fl[r, 0] = ninf
+            out[r, 1] = 0
+        out[r, 2:2 + nmax] = -1
+        fl[r, 2 + nmax:] = ninf
+        if n:
+            vals, idx = torch.sort(row, descending=True, stable=True)
+            out[r, 2:2 + n] = idx[:n].to(torch.int32)
+            if not dead:
+                fl[r, 2 + nmax:2 + nmax + n] = (vals[:n] - lse).float()
+    return out
+
+
 # --------------------------------------------------------------------------- sampling penalties
 # The device state of ops/penalties.py, on the same packed table: counts int16 [n_slots, Vs],
 # bit 15 = token in the prompt, bits 0..14 = occurrences among the generated tokens (saturating).

@@ -91,6 +91,47 @@ def logprobs(logits: torch.Tensor, tokens: torch.Tensor, n_top: torch.Tensor,
     return out
 
 
+PROMPT_LOGPROB_WORDS = 2 + 2 * LOGPROB_NMAX  # [logprob | rank | 20 ids | 20 logprobs]
+
+
+def prompt_logprobs(logits: torch.Tensor, targets: torch.Tensor, n_top: torch.Tensor,
+                    out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """logits [R, V] (bf16 or fp32), target ids int32 [R], ``n_top`` int32 [R] → packed int32
+    ``[R, PROMPT_LOGPROB_WORDS]``: the log-probability of ``targets[r]`` under row ``r``, its 1-based
+    rank in the total order (value descending, id ascending; 1 = the greedy token) and the top
+    list as :func:`logprobs` writes it.  A row with ``targets[r] < 0`` or ``n_top[r] < 0`` is left
+    untouched; ``targets[r] >= V`` reports logprob -inf and rank 0."""
+    R, V = logits.shape
+    if out is None:
+        out = torch.zeros((R, PROMPT_LOGPROB_WORDS), dtype=torch.int32, device=logits.device)
+    assert (out.dtype == torch.int32 and out.is_contiguous() and out.shape[0] >= R
+            and out.shape[1] == PROMPT_LOGPROB_WORDS)
+    if not logits.is_cuda:
+        return reference.prompt_logprobs(logits, targets, n_top, out)
+    assert logits.stride(-1) == 1 and logits.dtype in (torch.bfloat16, torch.float32)
+    assert targets.dtype == torch.int32 and n_top.dtype == torch.int32
+    assert targets.is_contiguous() and n_top.is_contiguous() and targets.numel() >= R and n_top.numel() >= R
+    dtype = 0 if logits.dtype == torch.bfloat16 else 1
+    native.call("pk_prompt_logprobs", out.data_ptr(), logits.data_ptr(), targets.data_ptr(), n_top.data_ptr(), R, V,
+                logits.stride(0), dtype, native.stream_ptr())
+    return out
+
+
+def unpack_prompt_logprobs(packed: torch.Tensor):
+    """Packed rows (on the host) → (logprob f32 [R], rank i32 [R], top ids i32 [R, 20], top logprobs
+    f32 [R, 20])."""
+    n = LOGPROB_NMAX
+    return (packed[:, 0].view(torch.float32), packed[:, 1], packed[:, 2:2 + n],
+            packed[:, 2 + n:].view(torch.float32))
+
+
+def prompt_logprob_entry(row, n: int):
+    """One packed row (numpy int32 [PROMPT_LOGPROB_WORDS]) → ``(logprob, rank, [(id, logprob) × n])``."""
+    f = row.view("float32")
+    k = LOGPROB_NMAX
+    return float(f[0]), int(row[1]), [(int(row[2 + j]), float(f[2 + k + j])) for j in range(n) if row[2 + j] >= 0]
+
+
 def unpack_logprobs(packed: torch.Tensor):
     """Packed rows (on the host) → (logprob f32 [B], top ids i32 [B, 20], top logprobs f32 [B, 20])."""
     n = LOGPROB_NMAX

@@ -71,6 +71,8 @@ class Metrics:
         self.kv_unforked = Counter("polykey_engine_kv_fork_undone_tokens_total", "forked prompt tokens handed back "
                                    "before their choice first ran (failed admission, a preemption) and prefilled "
                                    "after all", registry=r)
+        self.prompt_logprob_tokens = Counter("polykey_engine_prompt_logprob_tokens_total", "prompt tokens scored "
+                                             "for requests with prompt_logprobs / echo", registry=r)
         self._last: dict = {}
         self.cached_blocks = Gauge("polykey_engine_prefix_cache_blocks", "KV blocks registered in the prefix cache",
                                    registry=r)
@@ -118,6 +120,7 @@ class Metrics:
         self._advance(self.kv_fork_fallbacks, "kv_fork_fallbacks", getattr(engine, "kv_fork_fallbacks", 0))
         self._advance(self.kv_fork_shared, "kv_fork_shared", getattr(engine, "kv_fork_shared_tokens", 0))
         self._advance(self.kv_unforked, "kv_unforked", getattr(sch, "num_unforked_tokens", 0))
+        self._advance(self.prompt_logprob_tokens, "prompt_lp", getattr(engine, "prompt_logprob_tokens", 0))
         n = 0
         for o in outputs:
             n += len(o.new_token_ids)
