@@ -23,10 +23,12 @@ a measured activation peak — at 288 GB per MI355X an 8B model gets ~1.9 M cach
 """
 from __future__ import annotations
 
+import contextlib
 import dataclasses
 import logging
 import math
 import os
+import sys
 import threading
 import time
 from typing import Dict, List, Optional, Tuple
@@ -43,6 +45,27 @@ from ..ops import penalties as pen_ops
 from ..ops import sampler as sampler_ops
 from .scheduler import ScheduledBatch
 from .sequence import Sequence
+
+
+@contextlib.contextmanager
+def _capture(graph: "torch.cuda.CUDAGraph", pool=None):
+    """``torch.cuda.graph(graph, pool=pool)`` for a body that runs under inference mode, begun
+    outside it.  Beginning a capture registers the graph with the process-wide CUDA generator, and
+    the first graph registered creates the generator's graph-state tensors, which live as long as
+    any graph does and which every later capture in the process updates in place.  Created under
+    inference mode they are inference tensors, and a capture begun outside inference mode (another
+    library, a test) while an engine's graphs are still alive then fails, leaving the generator in
+    its capturing state.  Begun here, they are ordinary tensors whoever creates them."""
+    cm = torch.cuda.graph(graph, pool=pool)
+    with torch.inference_mode(False):
+        cm.__enter__()
+    try:
+        yield
+    except BaseException:
+        if not cm.__exit__(*sys.exc_info()):
+            raise
+    else:
+        cm.__exit__(None, None, None)
 
 
 @dataclasses.dataclass
@@ -1269,7 +1292,7 @@ class ModelRunner:
                 run()
             torch.cuda.current_stream(self.device).wait_stream(stream)
             graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph, pool=self.graph_pool):
+            with _capture(graph, self.graph_pool):
                 out = run()
             if self.graph_pool is None:
                 self.graph_pool = graph.pool()
@@ -1309,7 +1332,7 @@ class ModelRunner:
                 run()
             torch.cuda.current_stream(self.device).wait_stream(stream)
             graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph, pool=self.graph_pool):
+            with _capture(graph, self.graph_pool):
                 out = run()
             if self.graph_pool is None:
                 self.graph_pool = graph.pool()

@@ -7,13 +7,20 @@ import torch
 from polykey_service_amd.engine import EngineConfig, LLMEngine, SamplingParams
 from polykey_service_amd.models import build_model, get_config
 from polykey_service_amd.parallel.state import ParallelState
+from tests.model_cases import NORM_SEED, randomize_norms
 
 pytestmark = pytest.mark.gpu
+# norm-weight draws (tests/model_cases.py randomize_norms) per model: ones for which the CPU engine's first-token
+# top-2 margins stay at least 0.19 of the logits' rms on every prompt of the first-token comparisons, the
+# condition the model seeds were chosen by
+NORM_SEEDS = {"tiny-llama-gqa4": 93}
 
 
-def _models(name):
+def _models(name, norms=True):
     cfg = get_config(name)
     cpu = build_model(cfg, ParallelState(), torch.bfloat16, torch.device("cpu")).init_random(3)
+    if norms:
+        randomize_norms(cpu, NORM_SEEDS.get(name, NORM_SEED))  # before the copy: both engines share them
     gpu = copy.deepcopy(cpu).to("cuda")
     gpu.device = torch.device("cuda")
     return cpu, gpu
@@ -167,9 +174,15 @@ def test_folded_norm_decode_matches_normalised(monkeypatch):
 def test_packed_only_weights_match_row_major(monkeypatch):
     """70B-on-one-GPU mode: projections kept ONLY block-packed (row-major attributes become meta
     placeholders); prefill reads the packed layout through the MFMA prefill GEMM, decode through
-    the skinny GEMM.  Prefill logits match the engine holding row-major weights."""
-    _, ref_model = _models("tiny-llama-gqa4")
-    _, pk_model = _models("tiny-llama-gqa4")
+    the skinny GEMM.  Prefill logits match the engine holding row-major weights.
+
+    On init_random's unit norm weights: folding ones is exact, so the two engines round the same
+    values and differ by the GEMM kernel alone, which is what atol = 0.05 was sized for.  With
+    redrawn norm weights the packed engine rounds W diag(ln) and the row-major one rounds x * ln:
+    independent bf16 noise, up to 0.23 apart on logits of rms 1.9 while each is within 0.4 T of the
+    float64 model (tests/e2e/test_model_paths_gpu.py, which checks this mode with redrawn weights)."""
+    _, ref_model = _models("tiny-llama-gqa4", norms=False)
+    _, pk_model = _models("tiny-llama-gqa4", norms=False)
     prompts = [[1] + list(range(5, 5 + n)) for n in (70, 130, 257)]  # > 64-row prefill GEMMs
     logits = {}
     outs = {}
@@ -290,3 +303,39 @@ def test_fused_handoff_timeout_falls_back_to_two_launches(overlap, monkeypatch):
         gemm.set_fused_spin_limit(0)
         gemm.clear_fused_error()
         gemm.MLP_FUSED, gemm.QKV_ATTN_FUSED = saved
+
+
+def test_a_capture_outside_inference_mode_while_an_engine_holds_graphs():
+    """The engine captures its decode graphs under inference mode.  The first graph a process
+    registers creates the CUDA generator's graph-state tensors, which every later capture updates in
+    place for as long as any graph lives: had the engine created them as inference tensors, a capture
+    begun outside inference mode while the engine is alive would raise and leave the generator in
+    its capturing state for the rest of the process (model_runner._capture begins the engine's
+    captures outside inference mode).  Both kinds of capture work next to each other, in either order."""
+    _, gpu = _models("tiny-llama")
+
+    def engine():
+        return LLMEngine(EngineConfig(model="tiny-llama", max_num_seqs=4, max_num_batched_tokens=256, max_model_len=512,
+                                      hip_graphs=True, device="cuda"), ParallelState(device=torch.device("cuda")), model=gpu)
+    e = engine()
+    assert e.runner.graphs
+    x = torch.zeros(8, device="cuda")
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        x.add_(1)
+    torch.cuda.current_stream().wait_stream(side)
+    torch.cuda.synchronize()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        x.add_(1)
+    graph.replay()
+    torch.cuda.synchronize()
+    assert x.tolist() == [2.0] * 8
+    torch.rand(4, device="cuda")  # the generator is not left capturing
+    prompts = [[1, 7, 8, 9], [1, 30, 31]]
+    want = e.generate(prompts, SamplingParams(max_tokens=6, ignore_eos=True))
+    assert e.runner.stats["graph_steps"] > 0
+    e2 = engine()  # captured while a graph from outside inference mode is alive
+    assert e2.generate(prompts, SamplingParams(max_tokens=6, ignore_eos=True)) == want
+    assert e2.runner.stats["graph_steps"] > 0

@@ -14,14 +14,20 @@ from polykey_service_amd.engine import EngineConfig, LLMEngine, SamplingParams
 from polykey_service_amd.models import build_model, get_config
 from polykey_service_amd.ops import gemm
 from polykey_service_amd.parallel.state import ParallelState
+from tests.model_cases import NORM_SEED, randomize_norms
 
 pytestmark = pytest.mark.gpu
+# norm-weight draws (tests/model_cases.py randomize_norms) per model: ones for which the CPU engine's first-token
+# top-2 margins stay at least 0.19 of the logits' rms on every prompt of the first-token comparisons, the
+# condition the model seeds were chosen by
+NORM_SEEDS = {"tiny-mixtral": 0}
 FP8 = torch.float8_e4m3fn
 
 
 def _models(name, scales=None):
     cfg = get_config(name)
     cpu = build_model(cfg, ParallelState(), torch.bfloat16, torch.device("cpu")).init_random(3)
+    randomize_norms(cpu, NORM_SEEDS.get(name, NORM_SEED))  # before the copy: both engines share them
     for i, layer in enumerate(cpu.layers):
         if scales:
             layer.attn.k_scale, layer.attn.v_scale = scales[i % len(scales)]

@@ -13,6 +13,7 @@ from polykey_service_amd.engine import EngineConfig, LLMEngine, SamplingParams
 from polykey_service_amd.models import build_model, get_config
 from polykey_service_amd.models.lora import LoraAdapter
 from polykey_service_amd.parallel.state import ParallelState
+from tests.model_cases import NORM_SEED, randomize_norms
 
 pytestmark = pytest.mark.gpu
 FP8 = torch.float8_e4m3fn
@@ -23,6 +24,8 @@ NAMES = ["tiny-llama", "tiny-llama-gqa4"]
 SEEDS = {"tiny-llama": 5, "tiny-llama-gqa4": 2, ("tiny-llama", "auto"): 5, ("tiny-llama-gqa4", "auto"): 2,
          ("tiny-llama-gqa4", "fp8"): 2}
 B_STD = 0.08
+# the norm-weight draws (tests/model_cases.py randomize_norms) chosen with them, by the same conditions
+NORM_SEEDS = {("tiny-llama", "auto"): 12, ("tiny-llama-gqa4", "auto"): 4, ("tiny-llama-gqa4", "fp8"): 6}
 PROMPTS = [[1] + list(range(5, 5 + n)) for n in (3, 40, 77)]
 
 
@@ -34,9 +37,10 @@ def adapters(name):
             ("Z", LoraAdapter.random(cfg, rank=4, alpha=8, seed=3, b_std=0.0)))
 
 
-def models(name, seed=None):
+def models(name, seed=None, norms=NORM_SEED):
     seed = SEEDS[name] if seed is None else seed
     cpu = build_model(get_config(name), ParallelState(), torch.bfloat16, torch.device("cpu")).init_random(seed)
+    randomize_norms(cpu, norms)  # before the copy: both engines share them
     gpu = copy.deepcopy(cpu).to("cuda")
     gpu.device = torch.device("cuda")
     return cpu, gpu
@@ -128,7 +132,7 @@ def test_against_the_cpu_lora_engine(name, kv):
     engine's own adapter-versus-base distance on that prompt; and its GPU-versus-CPU error is at
     most twice the largest base-row GPU-versus-CPU error of the run (the base rows are existing
     code; the LoRA form adds one bf16 rounding per projection)."""
-    cpu, gpu = models(name, SEEDS[(name, kv)])
+    cpu, gpu = models(name, SEEDS[(name, kv)], NORM_SEEDS[(name, kv)])
     ec = engine(name, cpu, "cpu", graphs=False, kv_cache_dtype=kv)
     eg = engine(name, gpu, kv_cache_dtype=kv)
     assert (eg.runner.kv_caches[0][0].dtype == FP8) == (kv == "fp8")

@@ -29,6 +29,7 @@ from polykey_service_amd.models.lora import LoraAdapter
 from polykey_service_amd.ops import attention as A
 from polykey_service_amd.ops import gemm
 from polykey_service_amd.parallel.state import ParallelState
+from tests.model_cases import randomize_norms
 
 pytestmark = pytest.mark.gpu
 NAME = "tiny-qwen3"
@@ -45,6 +46,7 @@ def graph_logits(monkeypatch):
 
 def models(seed=3):
     cpu = build_model(get_config(NAME), ParallelState(), torch.bfloat16, torch.device("cpu")).init_random(seed)
+    randomize_norms(cpu)  # before the copy: both engines share them
     gpu = copy.deepcopy(cpu).to("cuda")
     gpu.device = torch.device("cuda")
     return cpu, gpu

@@ -15,6 +15,7 @@ import torch
 from polykey_service_amd.engine import EngineConfig, LLMEngine, SamplingParams
 from polykey_service_amd.models import build_model, get_config
 from polykey_service_amd.parallel.state import ParallelState
+from tests.model_cases import randomize_norms
 
 pytestmark = pytest.mark.gpu
 
@@ -48,10 +49,7 @@ def test_llama3_8b_width_prefill_and_fused_decode_match_cpu_reference(n):
     prompts = PROMPTS if n == 3 else MANY[n]
     cfg = dataclasses.replace(get_config("llama3-8b"), num_layers=2)
     cpu = build_model(cfg, ParallelState(), torch.bfloat16, torch.device("cpu")).init_random(11)
-    with torch.no_grad():
-        for layer in cpu.layers:
-            layer.ln1.copy_(torch.linspace(0.5, 1.5, layer.ln1.numel()).to(layer.ln1.dtype))
-            layer.ln2.copy_(torch.linspace(1.5, 0.5, layer.ln2.numel()).to(layer.ln2.dtype))
+    randomize_norms(cpu)  # ln1, ln2 and the final norm, before the copy
     gpu = copy.deepcopy(cpu).to("cuda")
     gpu.device = torch.device("cuda")
     ge = _engine(gpu, "cuda", cfg, len(prompts))

@@ -29,6 +29,7 @@ from polykey_service_amd.models.config import PRESETS
 from polykey_service_amd.ops import attention as A
 from polykey_service_amd.ops import gemm
 from polykey_service_amd.parallel.state import ParallelState
+from tests.model_cases import NORM_SEED, randomize_norms
 
 pytestmark = pytest.mark.gpu
 BOUND, BOUND_FP8 = 2.0 ** -3, 2.0 ** -2
@@ -37,6 +38,9 @@ MAX_TOKENS = 16
 G8 = "tiny-llama-g8-v1008"
 PRESETS.setdefault(G8, dataclasses.replace(PRESETS["tiny-llama-g8"], name=G8, vocab_size=1008))
 K_OF = {"tiny-llama": 3, G8: 1, "tiny-qwen3": 3}
+# norm-weight draws (tests/model_cases.py randomize_norms): for G8 one with which the CPU engine's first-token top-2
+# margins are at least 0.15 of the logits' rms on every prompt, so that both engines share token prefixes on all three
+NORM_SEEDS = {G8: 1}
 
 
 @pytest.fixture(autouse=True)
@@ -50,7 +54,9 @@ _MODELS = {}
 
 def models(name):
     if name not in _MODELS:
-        _MODELS[name] = build_model(get_config(name), ParallelState(), torch.bfloat16, torch.device("cpu")).init_random(3)
+        _MODELS[name] = randomize_norms(
+            build_model(get_config(name), ParallelState(), torch.bfloat16, torch.device("cpu")).init_random(3),
+            NORM_SEEDS.get(name, NORM_SEED))
     cpu = _MODELS[name]
     gpu = copy.deepcopy(cpu).to("cuda")
     gpu.device = torch.device("cuda")

@@ -12,13 +12,19 @@ from polykey_service_amd.engine import EngineConfig, LLMEngine, SamplingParams
 from polykey_service_amd.models import build_model, get_config
 from polykey_service_amd.ops import gemm, gemm_w8
 from polykey_service_amd.parallel.state import ParallelState
+from tests.model_cases import NORM_SEED, randomize_norms
 
 pytestmark = pytest.mark.gpu
+# norm-weight draws (tests/model_cases.py randomize_norms) per (model, model seed): ones for which the CPU
+# engine's first-token top-2 margins stay at least 0.19 of the logits' rms on every prompt of the first-token
+# comparisons, the condition the model seeds were chosen by
+NORM_SEEDS = {("tiny-llama", 5): 16, ("tiny-llama-gqa4", 2): 110}
 FP8 = torch.float8_e4m3fn
 
 
 def _models(name, seed=3):
     cpu = build_model(get_config(name), ParallelState(), torch.bfloat16, torch.device("cpu")).init_random(seed)
+    randomize_norms(cpu, NORM_SEEDS.get((name, seed), NORM_SEED))  # before the copy: both engines share them
     gpu = copy.deepcopy(cpu).to("cuda")
     gpu.device = torch.device("cuda")
     return cpu, gpu
@@ -105,7 +111,7 @@ def test_a_600_token_prompt_takes_the_wide_path_and_agrees_with_chunks(monkeypat
     step that second rounding moves the first-token logits by 0.022 of their rms (this model, this
     prompt): the bound is 2^-4, under three times that, against logits that differ between prompts
     by their full size.  The greedy token agrees: the seed is one for which the reference's top-2
-    margin on this prompt is 0.42 of the rms."""
+    margin on this prompt is 0.46 of the rms."""
     _, gpu = _models("tiny-llama-gqa4", 2)
     prompt = [1] + [(7 * i) % 200 + 2 for i in range(599)]
     wide_calls = []

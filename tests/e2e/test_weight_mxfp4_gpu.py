@@ -12,14 +12,20 @@ from polykey_service_amd.engine import EngineConfig, LLMEngine, SamplingParams
 from polykey_service_amd.models import build_model, get_config
 from polykey_service_amd.ops import gemm, gemm_w4
 from polykey_service_amd.parallel.state import ParallelState
+from tests.model_cases import NORM_SEED, randomize_norms
 
 pytestmark = pytest.mark.gpu
+# norm-weight draws (tests/model_cases.py randomize_norms) per (model, model seed): ones for which the CPU
+# engine's first-token top-2 margins stay at least 0.19 of the logits' rms on every prompt of the first-token
+# comparisons, the condition the model seeds were chosen by
+NORM_SEEDS = {("tiny-llama-gqa4", 6): 42}
 FP8 = torch.float8_e4m3fn
 MIN_MARGIN = 0.19  # top-2 margin of the reference's logits, in their rms, below which a token may flip
 
 
 def _models(name, seed=3):
     cpu = build_model(get_config(name), ParallelState(), torch.bfloat16, torch.device("cpu")).init_random(seed)
+    randomize_norms(cpu, NORM_SEEDS.get((name, seed), NORM_SEED))  # before the copy: both engines share them
     gpu = copy.deepcopy(cpu).to("cuda")
     gpu.device = torch.device("cuda")
     return cpu, gpu
